@@ -10,14 +10,20 @@ reach rank 0 through one RCCL gather per step.
   efficiency compares like with like. At N > 1 a step renders N independent C2 frames, one whole
   frame per GPU (seed + rank; weak scaling: no tile dealing, no load balancing), gathered on rank 0
   by one RCCL gather per step. At N = 1 there is no process group and no gather.
-* N > 1 also reports, as `secondary.c3_strong`, north_star's tile scaling of ONE frame: config C3
-  (2048x2048, 256 spp) split over the N GPUs as cost-dealt 64x64 tiles (strong scaling).
+* --full at N > 1 also reports, as `secondary.c3_strong`, north_star's tile scaling of ONE frame: config
+  C3 (2048x2048, 256 spp) split over the N GPUs as cost-dealt 64x64 tiles (strong scaling).
 * --config c3 / c5 select BASELINE.json's other configurations explicitly (their own scaling).
 
 Preprocess (tessellation, irradiance kernel, octree build) runs once before timing and is
 reported separately, as SURVEY.md §8d prescribes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5]
+A plain run does what `value` needs: set-up, W warmup steps, K timed steps, the result line.
+--full adds everything else the bench measures: the two traversal-count passes and the Mo()-gather
+roofline from them, the secondary figures (reference sampler, C3) and the CPU baseline.
+--dump-outputs DIR writes the film tiles of the last timed step (seeded inputs: the same from run
+to run) as DIR/film_tiles.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
   Without torchrun, --gpus N > 1 starts the N rank processes itself (before any GPU call).
 """
@@ -32,7 +38,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "pbrt-v2-skin_amd"))
 
-HBM_PEAK_GBS = 8000.0   # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak
 # SURVEY.md §8d algorithmic bytes of the Mo() gather: per octree record a query needs, position
 # 12 + area 4 + 4 bytes per band of E/Et (136 B for 30 bands). The sharded kernel visits
 # records per band group, so a step's bytes = 4 B x (record, band) evaluations summed over
@@ -60,6 +66,12 @@ VALU_CEILING_VARIANT = "gather mix r06 (row + LDS record, VALU + SALU)"
 # sources whose code the PMC summary's counters describe (profiles/*_pmc.json "source_hash")
 KERNEL_SOURCES = ("pbrt-v2-skin_amd/csrc/mo_kernel.hip", "pbrt-v2-skin_amd/csrc/mo_band.h",
                   "pbrt-v2-skin_amd/csrc/mo_wave.h", "pbrt-v2-skin_amd/csrc/octree.h")
+
+# --dump-outputs: a film buffer larger than the limit is written as DUMP_SAMPLE of its elements, drawn
+# once from a generator seeded with DUMP_SAMPLE_SEED (the same elements in every run of the same arguments)
+DUMP_LIMIT_BYTES = 48 << 20
+DUMP_SAMPLE = 8 << 20
+DUMP_SAMPLE_SEED = 20240229
 
 
 # BASELINE.json configs this bench runs: (label, resolution, spp, default scaling, mesh subdivision
@@ -147,6 +159,15 @@ def parse(argv=None):
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary figures (C3 strong scaling at N > 1; the reference-sampler C2 frame at N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the traversal-count passes and the Mo()-gather roofline, the secondary "
+                         "figures and the CPU baseline (--no-secondary / --no-cpu-baseline drop the latter two). "
+                         "Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (the film tile buffers of "
+                         "rank 0: its own at one GPU, every rank's gathered ones otherwise) as DIR/film_tiles.npy, "
+                         "float32; a buffer over %d MiB is written as a fixed seeded sample of its elements"
+                         % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--out", default=None, help="write rank 0's first frame as .pfm/.exr")
     ap.add_argument("--pmc-json", default=None,
                     help="rocprofv3 PMC summary (tools/summarize_prof.py) of this bench command; default: the "
@@ -314,36 +335,150 @@ def main(a):
     seeds = [a.seed + f for f in range(frames)]
     stream = torch.cuda.current_stream().cuda_stream
 
-    # traversal-count pass (untimed): octree records the Mo gather reads for this workload
-    out_c = torch.zeros((max(1, len(mine)), T * T * 4), dtype=torch.float32, device="cuda")
-    ctx.set_instrumentation(kernel_timing=False, count_traversal=True)
-    ctx.reset_render_stats()
-    tl.render_items(ctx, mine, tiles, sc.spp, seeds, out_c, T, stream)
-    cnt = ctx.render_stats()
-    # the reference traversal's record visits: the same pass with the reach pruning off
-    ctx.set_instrumentation(kernel_timing=False, count_traversal=2)
-    ctx.reset_render_stats()
-    tl.render_items(ctx, mine, tiles, sc.spp, seeds, out_c, T, stream)
-    cnt_ref = ctx.render_stats()
-    del out_c
+    cnt = cnt_ref = None
+    if a.full:
+        cnt, cnt_ref = count_passes(ctx, mine, tiles, sc.spp, seeds, T, stream)
+    # the per-kernel HIP events stay on in the timed steps of a plain run too: `value` times the same
+    # region with or without --full
     ctx.set_instrumentation(kernel_timing=True, count_traversal=False)
     ctx.reset_render_stats()
     dt, gath, out = timed_steps(a, ctx, sc, tiles, items_by_rank, frames, T, rank, world, a.steps, a.warmup)
     st = ctx.render_stats()
     ctx.set_instrumentation(kernel_timing=False, count_traversal=False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, gath if gath is not None else [out])
 
     samples_per_step = frames * sc.xres * sc.yres * sc.spp
     value = samples_per_step * a.steps / dt / 1e6
-    # SSS-shaded samples (camera samples that run the Mo() gather): counted on every rank
-    sss = torch.tensor([cnt["sss_samples"], cnt["samples"]], dtype=torch.float64, device="cuda")
-    if world > 1:
-        dist.all_reduce(sss)
-    sss_per_step, traced_per_step = float(sss[0].item()), float(sss[1].item())
-    # dominant kernel + Mo gather roofline (per-launch averages over the timed region, this rank)
+    # per-kernel times of the timed region (per-launch sums over its steps, this rank)
     kern = {"primary": (st["ms_camera"], st["n_camera"]), "shade_direct": (st["ms_direct"], st["n_direct"]),
             "shade_tex": (st["ms_tex"], st["n_tex"]), "replay": (st["ms_replay"], st["n_replay"]),
             "mo_band": (st["ms_shade"], st["n_shade"]),
             "film": (st["ms_film"], st["n_film"])}
+    kernel_ms_per_step = {k: round(v[0] / a.steps, 3) for k, v in kern.items()}
+
+    sss_per_step = traced_per_step = 0.0
+    roofline, mo_gbs = None, 0.0
+    if a.full:
+        # SSS-shaded samples (camera samples that run the Mo() gather): counted on every rank
+        sss = torch.tensor([cnt["sss_samples"], cnt["samples"]], dtype=torch.float64, device="cuda")
+        if world > 1:
+            dist.all_reduce(sss)
+        sss_per_step, traced_per_step = float(sss[0].item()), float(sss[1].item())
+        roofline, mo_gbs = gather_roofline(a, st, cnt, cnt_ref, kern, kernel_ms_per_step)
+
+    secondary = None
+    if a.full and world > 1 and a.config == "c2" and not a.no_secondary:
+        secondary = c3_strong_secondary(a, rank, world, local)
+    if a.full and world == 1 and a.config == "c2" and a.sampler == "hash" and not a.no_secondary:
+        # pbrt's own sampler on the same frame, and C3's frame on this one GPU: the N = 1 anchor of the
+        # c3_strong series the N > 1 lines carry
+        secondary = reference_sampler_secondary(a, local)
+        secondary.update(c3_strong_secondary(a, rank, world, local))
+
+    cpu = None
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
+        cpu = cpu_baseline(sc, ctx, a)
+
+    if rank == 0:
+        line = {"metric": "Msamples/s (%s pixel loop) + Mo()-gather roofline" % ("skin.pbrt C2" if a.config == "c2"
+                                                                                 else a.config.upper()),
+                "value": round(value, 3),
+                "unit": "Msamples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+                "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": scaling,
+                "vs_baseline": None, "dtype": "f32",
+                "data": "synthetic (reconstructed %s, head.pbrt mesh%s%s)" % (
+                    os.path.basename(a.scene), ", subdivided" if subdiv else "", ", rgbprofile" if a.rgb_profile else "")
+                    + (", pbrt's sampler replayed" if a.sampler == "reference" else ""),
+                "config": {"workload": "%s (%dx%d, %d spp%s), %dx%d tiles%s%s"
+                           % (label, sc.xres, sc.yres, sc.spp, " per GPU" if scaling == "weak" else "", T, T,
+                              ", independent whole frames, one per GPU" if frames == world and world > 1 else
+                              (" dealt by cost" if world > 1 else ""),
+                              ", one RCCL film gather per step" if world > 1 else ""),
+                           "scene": os.path.basename(a.scene), "rgb_profile": bool(a.rgb_profile),
+                           "sampler": a.sampler if a.sampler == "hash" else "reference (%d cores)" % a.replay_cores,
+                           "frames_per_step": frames, "triangles": int(sum(len(me["indices"]) for me in sc.meshes)),
+                           "irradiance_points": n_points, "preprocess_s": round(t_pre, 3),
+                           "material_build_s": round(t_materials, 3), "tile_deal_s": round(t_deal, 3),
+                           "tiles": len(tiles), "skin_tiles": skin_tiles, "deal_balance": round(deal_balance, 4),
+                           "mo_common_grid": bool(ctx.gather_info(0)["common_grid"]) if sc.materials else False}}
+        if a.full:
+            line["config"].update(count_figures(cnt, sss_per_step, traced_per_step, a.steps, dt, mo_gbs))
+            line["roofline"] = roofline
+            line["cpu_baseline"] = cpu
+            if secondary:
+                line["secondary"] = secondary
+        else:
+            line["kernel_ms_per_step"] = kernel_ms_per_step
+        print(json.dumps(line), flush=True)
+    if a.out and rank == 0:
+        from mpss import film
+        img = np.zeros((frames, sc.yres, sc.xres, 4), np.float32)
+        g = [x.cpu().numpy() for x in gath] if gath is not None else [out.cpu().numpy()]
+        tl.assemble(img, g, items_by_rank, tiles, T)
+        rgb = film.finalize(img[0])
+        film.write_image(a.out, rgb)
+    ctx.close()
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def count_passes(ctx, mine, tiles, spp, seeds, T, stream):
+    """The two untimed traversal-count passes of --full: (the gather's own record visits, the reference
+    traversal's)."""
+    import torch
+    from mpss import tiles as tl
+    # traversal-count pass (untimed): octree records the Mo gather reads for this workload
+    out_c = torch.zeros((max(1, len(mine)), T * T * 4), dtype=torch.float32, device="cuda")
+    ctx.set_instrumentation(kernel_timing=False, count_traversal=True)
+    ctx.reset_render_stats()
+    tl.render_items(ctx, mine, tiles, spp, seeds, out_c, T, stream)
+    cnt = ctx.render_stats()
+    # the reference traversal's record visits (SURVEY 8d): the same pass with the reach pruning off
+    ctx.set_instrumentation(kernel_timing=False, count_traversal=2)
+    ctx.reset_render_stats()
+    tl.render_items(ctx, mine, tiles, spp, seeds, out_c, T, stream)
+    cnt_ref = ctx.render_stats()
+    return cnt, cnt_ref
+
+
+def dump_outputs(path, bufs):
+    """--dump-outputs: the film tile buffers of the last timed step ([slots, T*T*4] float32 per rank,
+    stacked over the ranks) as path/film_tiles.npy. A buffer over DUMP_LIMIT_BYTES is written as
+    DUMP_SAMPLE of its elements at fixed seeded positions (ascending), the same in every run."""
+    import numpy as np
+    import torch
+    arr = torch.stack(list(bufs)).cpu().numpy().astype(np.float32, copy=False)
+    if arr.nbytes > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, arr.size, DUMP_SAMPLE))
+        arr = arr.reshape(-1)[idx]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "film_tiles.npy"), arr)
+
+
+def count_figures(cnt, sss_per_step, traced_per_step, steps, dt, mo_gbs):
+    """The result line's config entries that come from the traversal-count passes (--full)."""
+    return {"sss_hit_fraction": round(sss_per_step / max(1.0, traced_per_step), 4),
+            "sss_samples_per_s": round(sss_per_step * steps / dt, 1),
+            "mo_algorithmic_gbs": round(mo_gbs, 1), "mo_sss_samples": cnt["sss_samples"],
+            "mo_record_visits_per_sss_sample": round((cnt["mo_nodes"] + cnt["mo_points"]) /
+                                                     max(1, cnt["sss_samples"]), 2),
+            "mo_group_visits": [x + y for x, y in zip(cnt["group_nodes"], cnt["group_points"])],
+            "mo_lane_efficiency": round((cnt["mo_nodes"] + cnt["mo_points"]) /
+                                        max(1, 64 * (cnt["mo_wave_node_iters"] + cnt["mo_wave_point_iters"])), 4),
+            "mo_lookup_near_fraction": [round(x / max(1, cnt["mo_lookups"]), 4) for x in cnt["mo_lookups_near"]],
+            "mo_wave_iters": {"node": cnt["mo_wave_node_iters"], "point": cnt["mo_wave_point_iters"]},
+            "mo_lane_records": {"rows": cnt["mo_row_lane_records"], "lds": cnt["mo_lds_lane_records"],
+                                "tables": cnt["mo_table_lane_records"]},
+            "mo_l2_footprint": l2_footprint(cnt),
+            "mo_visits": {"node": cnt["mo_nodes"], "point": cnt["mo_points"],
+                          "lookups_in_profile": cnt["mo_lookups"]}}
+
+
+def gather_roofline(a, st, cnt, cnt_ref, kern, kernel_ms_per_step):
+    """--full: the dominant kernel and the Mo() gather's roofline (per-launch averages over the timed
+    region, this rank) from the timed steps' kernel times `st` and the count passes; returns (the
+    result line's `roofline`, the SURVEY 8d algorithmic GB/s)."""
     dom = max(kern, key=lambda k: kern[k][0])
     nbands = [sum(1 for c in grp if c >= 0) for grp in cnt["group_bands"]]
     gvis = [cnt["group_nodes"][g] + cnt["group_points"][g] for g in range(8)]
@@ -379,7 +514,7 @@ def main(a):
                                         % (ref_visits / max(1, cnt["sss_samples"]))},
                 "kernel_eval_bytes_per_launch": kern_bytes_step / launches_per_step,
                 "dominant_kernel": dom,
-                "kernel_ms_per_step": {k: round(v[0] / a.steps, 3) for k, v in kern.items()}}
+                "kernel_ms_per_step": kernel_ms_per_step}
     if pt:
         roofline["traffic"] = pt.get("traffic")
         roofline["traffic_source"] = pt["source"]
@@ -395,73 +530,7 @@ def main(a):
             roofline["hbm_gbs"] = round(roofline["traffic"] / (shade_launch_ms * 1e-3) / 1e9, 1)
             roofline["hbm_frac"] = round(roofline["hbm_gbs"] / HBM_PEAK_GBS, 4)
         headline_bound(roofline, pt, shade_launch_ms)
-
-    secondary = None
-    if world > 1 and a.config == "c2" and not a.no_secondary:
-        secondary = c3_strong_secondary(a, rank, world, local)
-    if world == 1 and a.config == "c2" and a.sampler == "hash" and not a.no_secondary:
-        # pbrt's own sampler on the same frame, and C3's frame on this one GPU: the N = 1 anchor of the
-        # c3_strong series the N > 1 lines carry
-        secondary = reference_sampler_secondary(a, local)
-        secondary.update(c3_strong_secondary(a, rank, world, local))
-
-    cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(sc, ctx, a)
-
-    if rank == 0:
-        line = {"metric": "Msamples/s (%s pixel loop) + Mo()-gather roofline" % ("skin.pbrt C2" if a.config == "c2"
-                                                                                 else a.config.upper()),
-                "value": round(value, 3),
-                "unit": "Msamples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-                "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": scaling,
-                "vs_baseline": None, "dtype": "f32",
-                "data": "synthetic (reconstructed %s, head.pbrt mesh%s%s)" % (
-                    os.path.basename(a.scene), ", subdivided" if subdiv else "", ", rgbprofile" if a.rgb_profile else "")
-                    + (", pbrt's sampler replayed" if a.sampler == "reference" else ""),
-                "config": {"workload": "%s (%dx%d, %d spp%s), %dx%d tiles%s%s"
-                           % (label, sc.xres, sc.yres, sc.spp, " per GPU" if scaling == "weak" else "", T, T,
-                              ", independent whole frames, one per GPU" if frames == world and world > 1 else
-                              (" dealt by cost" if world > 1 else ""),
-                              ", one RCCL film gather per step" if world > 1 else ""),
-                           "scene": os.path.basename(a.scene), "rgb_profile": bool(a.rgb_profile),
-                           "sampler": a.sampler if a.sampler == "hash" else "reference (%d cores)" % a.replay_cores,
-                           "frames_per_step": frames, "triangles": int(sum(len(me["indices"]) for me in sc.meshes)),
-                           "irradiance_points": n_points, "preprocess_s": round(t_pre, 3),
-                           "material_build_s": round(t_materials, 3), "tile_deal_s": round(t_deal, 3),
-                           "tiles": len(tiles), "skin_tiles": skin_tiles, "deal_balance": round(deal_balance, 4),
-                           "sss_hit_fraction": round(sss_per_step / max(1.0, traced_per_step), 4),
-                           "sss_samples_per_s": round(sss_per_step * a.steps / dt, 1),
-                           "mo_algorithmic_gbs": round(mo_gbs, 1), "mo_sss_samples": cnt["sss_samples"],
-                           "mo_record_visits_per_sss_sample": round((cnt["mo_nodes"] + cnt["mo_points"]) /
-                                                                    max(1, cnt["sss_samples"]), 2),
-                           "mo_group_visits": [x + y for x, y in zip(cnt["group_nodes"], cnt["group_points"])],
-                           "mo_lane_efficiency": round((cnt["mo_nodes"] + cnt["mo_points"]) /
-                                                       max(1, 64 * (cnt["mo_wave_node_iters"] +
-                                                                    cnt["mo_wave_point_iters"])), 4),
-                           "mo_lookup_near_fraction": [round(x / max(1, cnt["mo_lookups"]), 4)
-                                                       for x in cnt["mo_lookups_near"]],
-                           "mo_wave_iters": {"node": cnt["mo_wave_node_iters"], "point": cnt["mo_wave_point_iters"]},
-                           "mo_common_grid": bool(ctx.gather_info(0)["common_grid"]) if sc.materials else False,
-                           "mo_lane_records": {"rows": cnt["mo_row_lane_records"], "lds": cnt["mo_lds_lane_records"],
-                                                  "tables": cnt["mo_table_lane_records"]},
-                           "mo_l2_footprint": l2_footprint(cnt),
-                           "mo_visits": {"node": cnt["mo_nodes"], "point": cnt["mo_points"],
-                                         "lookups_in_profile": cnt["mo_lookups"]}},
-                "roofline": roofline, "cpu_baseline": cpu}
-        if secondary:
-            line["secondary"] = secondary
-        print(json.dumps(line), flush=True)
-    if a.out and rank == 0:
-        from mpss import film
-        img = np.zeros((frames, sc.yres, sc.xres, 4), np.float32)
-        g = [x.cpu().numpy() for x in gath] if gath is not None else [out.cpu().numpy()]
-        tl.assemble(img, g, items_by_rank, tiles, T)
-        rgb = film.finalize(img[0])
-        film.write_image(a.out, rgb)
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return roofline, mo_gbs
 
 
 def l2_footprint(cnt):

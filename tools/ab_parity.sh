@@ -28,7 +28,7 @@ for r in $(seq 1 $ROUNDS); do
   for v in ${VARIANTS:-A B}; do
     cp ab/libmpss_$v.so $lib
     log=gpurun_out/${TAG}_ab_${v}${r}.log
-    timeout -k 10 600 python -u bench.py --config c2 --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $log 2>&1 || { echo "bench $v$r failed"; tail -20 $log; restore; exit 1; }
+    timeout -k 10 600 python -u bench.py --config c2 --steps 3 --warmup 1 --full --no-cpu-baseline --no-secondary > $log 2>&1 || { echo "bench $v$r failed"; tail -20 $log; restore; exit 1; }
     python3 -c 'import json,sys; d=json.loads([l for l in open(sys.argv[1]) if "\"metric\"" in l][0]); print(sys.argv[2], d["value"], d["roofline"]["kernel_ms_per_step"]["mo_band"], d["config"]["mo_l2_footprint"]["per_sss_sample"]["rows"]["lines"], d["config"]["mo_l2_footprint"]["per_sss_sample"]["tables"]["lines"])' $log $v$r | tee -a $out
   done
 done
