@@ -11,6 +11,8 @@
  *   mpss_add_layeredskin            CreateLayeredSkinMaterial + LayeredSkin::LayeredSkin parse-time
  *                                   precompute (src/materials/layeredskin.cpp:39-123, 222-262;
  *                                   src/core/multipole.cpp:241-295, 371-406, 466-549)
+ *   mpss_update_layeredskin         the same precompute for new parameters, in place (a pigment sweep
+ *                                   re-renders one scene; src/materials/layeredskin.cpp:39-123)
  *   mpss_set_material_tables        MultipoleBSSRDFData(pData, rhoData) for externally built tables
  *                                   (src/core/multipole.h:44-59)
  *   mpss_get_material_tables        read back Profile::data / rcpDsqSpacing / RhoData::hd
@@ -179,6 +181,25 @@ typedef struct {
 void mpss_layeredskin_defaults(mpss_layeredskin *m);
 /* Builds the 30-band multipole profile and the 1025-entry rho_hd table; returns a material id. */
 int mpss_add_layeredskin(mpss_ctx *ctx, const mpss_layeredskin *m, uint32_t *material_id);
+/* Rebuilds material `material_id` in place for new LayeredSkin parameters: exactly what
+ * mpss_add_layeredskin builds for *m (LayeredSkin::LayeredSkin's precompute, layeredskin.cpp:39-123:
+ * profile, rho table, rgb tables, common grids, every switch of mpss_layeredskin), under the same id,
+ * with the material's texture bindings and the meshes bound to it kept -- the step between two frames
+ * of a pigment sweep, where geometry, lights and camera stay. Targets: materials made by
+ * mpss_add_layeredskin or mpss_set_material_tables; an unknown id or a dipole material is
+ * MPSS_ERR_INVALID. Serialised like every mutator (it waits for in-flight mpss_render_tile(s) /
+ * mpss_mo_batch calls and their kernels before anything they read is replaced). Only the materials'
+ * device records are uploaded again: BVH, meshes, lights, textures and camera bins stay. The
+ * irradiance and octree of an earlier mpss_preprocess go stale: mpss_render_tile(s) and mpss_tile_costs
+ * return MPSS_ERR_INVALID until mpss_preprocess has run again (which reuses its surface points: they
+ * do not depend on the material's tables); mpss_mo_batch keeps working on the octree the context
+ * holds, with the new profile. The context lock is held for the whole build (about 0.1 s at
+ * desiredlength 512): concurrent calls on the context wait that long. Callers must not run it between the two calls of a sizes-first query
+ * (mpss_get_material_tables, mpss_get_common_grid) of the same material. */
+int mpss_update_layeredskin(mpss_ctx *ctx, uint32_t material_id, const mpss_layeredskin *m);
+/* Monotonic counts since mpss_create: counts[0] scene uploads (BVH builds), [1] surface point-set
+ * builds (tessellation or the Poisson finder), [2] material table builds, [3] octree builds. */
+int mpss_build_counts(mpss_ctx *ctx, uint64_t counts[4]);
 /* Install precomputed tables: rd_table is channel-major [30][length]; rcp[30] = rcpDsqSpacing;
  * rho_hd[n_rho] (scalar, replicated over bands); albedo[30]. */
 int mpss_set_material_tables(mpss_ctx *ctx, const float *rd_table, uint32_t length, const float *rcp,
@@ -344,6 +365,12 @@ int mpss_get_render_stats(mpss_ctx *ctx, mpss_render_stats *out);
 /* Switch kernel_timing / count_traversal (0, 1 or 2, as mpss_config) after creation
  * (instrumented passes). */
 int mpss_set_instrumentation(mpss_ctx *ctx, int kernel_timing, int count_traversal);
+/* Which builder later material builds (mpss_add_layeredskin, mpss_update_layeredskin,
+ * mpss_set_material_tables) use for the common grids' per-knot error scan, the part of the grid build
+ * that grows with the table length: on_host 1 the host threads, 0 (default) the GPU, from the table
+ * already on the device. The grids are the same bit for bit (mpss_get_common_grid against
+ * mpss_host_common_grid). */
+int mpss_set_grid_builder(mpss_ctx *ctx, int on_host);
 int mpss_reset_render_stats(mpss_ctx *ctx);
 
 /* ---- Monte-Carlo layered profile (renderer "mcprofile", src/renderers/mcprofile.cpp) ---- */
@@ -411,6 +438,13 @@ int mpss_host_common_grid(const float *table, uint32_t L, const float *rcp, int 
                           uint32_t *n_rows, int32_t *bands, float *rg, float *u0lim, float *u1lim, float *u1start,
                           uint32_t *row0, uint32_t *ubase, float *rel_err, float *l1_err, float *ua, float *hinv,
                           int *ok);
+/* The common grid the context built for material `material_id` and the LDS layout near_field (5088 or
+ * 10236; both are built when the material is): outputs and their meaning as mpss_host_common_grid,
+ * sizes first with rows NULL. *ok = 0 (and no rows) when the builder declined and the per-band tables
+ * are in use. A dipole material has none (MPSS_ERR_INVALID). */
+int mpss_get_common_grid(mpss_ctx *ctx, uint32_t material_id, int near_field, float *rows, uint32_t *n_rows,
+                         int32_t *bands, float *rg, float *u0lim, float *u1lim, float *u1start, uint32_t *row0,
+                         uint32_t *ubase, float *rel_err, float *l1_err, float *ua, float *hinv, int *ok);
 /* Octree build + pre-order export (sizes first with NULL outputs). */
 int mpss_host_octree_export(uint32_t n, const float *p, const float *nrm, const float *E, const float *area,
                             uint32_t *n_nodes, float *node_p, float *node_area, float *node_et, int32_t *depth,

@@ -168,7 +168,9 @@ void Context::mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, 
 void Context::activate() const { MPSS_HIP(hipSetDevice(cfg_.device)); }
 
 void Context::gather_info(uint32_t id, int *common_grid, float *rel_err, float *l1_err) const {
-    const Material &m = material(id);  // (takes mu_; materials are never replaced)
+    std::lock_guard<std::mutex> g(mu_);  // (a material may be rebuilt in place: read it under the lock)
+    if (id >= materials_.size()) throw Error(MPSS_ERR_INVALID, "unknown material id " + std::to_string(id));
+    const Material &m = *materials_[id];
     const bool band = !m.dipole;  // (rgbprofile: the grid of its R, G, B profiles, rel/l1_err[0..2])
     const int lay = cfg_.mo_near_field == 10236 ? 0 : 1;  // the grid of the configured LDS layout
     const bool on = band && cfg_.exact_mo == 0 && cfg_.mo_common_grid != 0 &&
@@ -180,13 +182,70 @@ void Context::gather_info(uint32_t id, int *common_grid, float *rel_err, float *
     }
 }
 
+void Context::material_tables(uint32_t id, float *rd, uint32_t *len, float *rcp, float *rho, uint32_t *n_rho,
+                              float *total) const {
+    std::lock_guard<std::mutex> g(mu_);
+    if (id >= materials_.size()) throw Error(MPSS_ERR_INVALID, "unknown material id " + std::to_string(id));
+    const Material &m = *materials_[id];
+    *len = (uint32_t)m.profile.length;
+    *n_rho = (uint32_t)m.rho.hd.size();
+    if (rd) memcpy(rd, m.profile.table.data(), sizeof(float) * m.profile.table.size());
+    if (rcp) memcpy(rcp, m.profile.rcp, sizeof(float) * NB);
+    if (rho) memcpy(rho, m.rho.hd.data(), sizeof(float) * m.rho.hd.size());
+    if (total) memcpy(total, m.profile.total_reflectance, sizeof(float) * NB);
+}
+
+void Context::common_grid(uint32_t id, int near_field, float *rows, uint32_t *n_rows, int32_t *bands, float *rg,
+                          float *u0lim, float *u1lim, float *u1start, uint32_t *row0, uint32_t *ubase,
+                          float *rel_err, float *l1_err, float *ua, float *hinv, int *ok) const {
+    activate();
+    std::lock_guard<std::mutex> g(mu_);
+    if (id >= materials_.size()) throw Error(MPSS_ERR_INVALID, "unknown material id " + std::to_string(id));
+    const Material &m = *materials_[id];
+    if (m.dipole) throw Error(MPSS_ERR_INVALID, "material " + std::to_string(id) + " is a dipole: it has no common grid");
+    const DeviceProfile &p = m.dev_profile;
+    const int lay = near_field == 10236 ? 0 : 1;
+    const CommonGrid &cg = lay == 0 ? p.cg : p.cg_half;
+    const DevBuf<float4> &tab = lay == 0 ? p.ctab : p.ctab_half;
+    *ok = cg.on ? 1 : 0;
+    const size_t nr = tab.n / 2;  // two float4 per row
+    if (n_rows) {
+        if (rows && *n_rows < nr) throw Error(MPSS_ERR_INVALID, "mpss_get_common_grid: rows too small");
+        *n_rows = (uint32_t)nr;
+    }
+    if (rows && nr) MPSS_HIP(hipMemcpy(rows, tab.ptr, sizeof(float4) * 2 * nr, hipMemcpyDeviceToHost));
+    for (int k = 0; k < kGroups; ++k) {
+        for (int j = 0; j < 4; ++j)  // (rgbprofile: its R, G, B in slots 0..2 of every group, set_rgb)
+            if (bands) bands[4 * k + j] = m.rgb ? (j < 3 ? j : -1) : p.groups.band[k][j];
+        if (rg) rg[k] = cg.rg[k];
+        if (u0lim) u0lim[k] = cg.u0lim[k];
+        if (u1lim) u1lim[k] = cg.u1lim[k];
+        if (u1start) u1start[k] = cg.u1start[k];
+        if (row0) row0[k] = cg.row0[k];
+        if (ubase) ubase[k] = cg.ubase[k];
+        if (ua) ua[k] = cg.ua[k];
+        if (hinv) hinv[k] = cg.hinv[k];
+    }
+    for (int c = 0; c < NB; ++c) {
+        if (rel_err) rel_err[c] = p.cg_rel_err[lay][c];
+        if (l1_err) l1_err[c] = p.cg_l1_err[lay][c];
+    }
+}
+
+void Context::build_counts(uint64_t counts[4]) const {
+    std::lock_guard<std::mutex> g(mu_);
+    counts[0] = n_scene_uploads_;
+    counts[1] = n_point_builds_;
+    counts[2] = n_material_builds_;
+    counts[3] = n_octree_builds_;
+}
+
 // Material ids travel in 8 bits of the render path's per-sample records (render.h REC_MAT_SHIFT).
 constexpr size_t kMaxMaterials = 256;
 
-uint32_t Context::add_layeredskin(const mpss_layeredskin &m) {
-    activate();
-    std::lock_guard<std::mutex> g(mu_);
-    if (materials_.size() >= kMaxMaterials) throw Error(MPSS_ERR_INVALID, "at most 256 materials per context");
+// LayeredSkin::LayeredSkin's parse-time precompute (layeredskin.cpp:39-123) into a Material of its own
+// device buffers (mu_ held; nothing of the context changes)
+std::unique_ptr<Material> Context::build_layeredskin(const mpss_layeredskin &m) {
     auto mat = std::make_unique<Material>();
     SkinParams sp;
     sp.roughness = m.roughness;
@@ -252,7 +311,8 @@ uint32_t Context::add_layeredskin(const mpss_layeredskin &m) {
     // Ft = 1 in Li (multipolesubsurface.cpp:285); MultipoleBSSRDFData(..., useMonteCarloProfile) keeps the
     // flag whichever profile was prepared (layeredskin.cpp:116)
     mat->is_monte_carlo = m.use_monte_carlo != 0;
-    mat->dev_profile.upload(mat->profile.table.data(), mat->profile.length, mat->profile.rcp, cfg_.mo_band_dealing == 1);
+    mat->dev_profile.upload(mat->profile.table.data(), mat->profile.length, mat->profile.rcp, cfg_.mo_band_dealing == 1,
+                             grid_on_host_);
     if (mat->rgb) {
         mat->dev_rgb.upload(mat->profile.table.data(), 3 * (size_t)mat->profile.length);
         for (int k = 0; k < 3; ++k) mat->rgb_rcp[k] = mat->profile.rcp[k];
@@ -260,10 +320,51 @@ uint32_t Context::add_layeredskin(const mpss_layeredskin &m) {
         mat->dev_profile.set_rgb(mat->profile.table.data());  // the sharded gather's three lookups + FromRGB
     }
     mat->dev_rho.upload(mat->rho.hd.data(), mat->rho.hd.size());
-    materials_.push_back(std::move(mat));
-    scene_dirty_ = true;
+    ++n_material_builds_;
+    return mat;
+}
+
+uint32_t Context::add_layeredskin(const mpss_layeredskin &m) {
+    activate();
+    std::lock_guard<std::mutex> g(mu_);
+    if (materials_.size() >= kMaxMaterials) throw Error(MPSS_ERR_INVALID, "at most 256 materials per context");
+    materials_.push_back(build_layeredskin(m));
+    mark_scene_dirty_locked();
     ensure_layouts();
     return (uint32_t)materials_.size() - 1;
+}
+
+// The material's tables, common grids and RenderMaterial record are replaced; the scene buffers (BVH,
+// meshes, lights, textures, camera bins) and scene_gen_ stay -- the replay cursors depend on camera
+// and geometry only.
+void Context::update_layeredskin(uint32_t id, const mpss_layeredskin &m) {
+    activate();
+    std::lock_guard<std::mutex> g(mu_);
+    if (id >= materials_.size())
+        throw Error(MPSS_ERR_INVALID, "mpss_update_layeredskin: unknown material id " + std::to_string(id));
+    if (materials_[id]->dipole)
+        throw Error(MPSS_ERR_INVALID, "mpss_update_layeredskin: material " + std::to_string(id) +
+                                          " is a dipole Rd functor, not a profile material");
+    std::unique_ptr<Material> mat = build_layeredskin(m);  // (its own buffers: nothing in use is touched yet)
+    quiesce_locked();  // no render / mo_batch may still read the old tables, layouts or d_materials_
+    const Material &old = *materials_[id];
+    mat->albedo_tex = old.albedo_tex;
+    mat->bump_tex = old.bump_tex;
+    // (neither point finder reads a material's BSSRDF state today; dropped all the same when it flips)
+    if (mat->no_bssrdf != old.no_bssrdf) invalidate_points_locked();
+    materials_[id] = std::move(mat);
+    materials_dirty_ = true;
+    if (preprocessed_) irradiance_stale_ = true;
+    // band layouts follow the profile's rcp: those of a grouping no material has any more are freed
+    // (a long sweep does not accumulate them), the new grouping's is built
+    auto &lays = dev_octree_.layouts;
+    for (size_t i = lays.size(); i-- > 0;) {
+        bool used = false;
+        for (const auto &mp : materials_)
+            used = used || (!mp->dipole && same_groups(lays[i]->groups, mp->dev_profile.groups));
+        if (!used) lays.erase(lays.begin() + (std::ptrdiff_t)i);
+    }
+    ensure_layouts();
 }
 
 uint32_t Context::set_material_tables(const float *rd, uint32_t len, const float *rcp, const float *rho,
@@ -286,10 +387,12 @@ uint32_t Context::set_material_tables(const float *rd, uint32_t len, const float
         mat->Kt[c] = 0.f;
     }
     mat->is_monte_carlo = is_mc;
-    mat->dev_profile.upload(mat->profile.table.data(), mat->profile.length, mat->profile.rcp, cfg_.mo_band_dealing == 1);
+    mat->dev_profile.upload(mat->profile.table.data(), mat->profile.length, mat->profile.rcp, cfg_.mo_band_dealing == 1,
+                             grid_on_host_);
     mat->dev_rho.upload(mat->rho.hd.data(), mat->rho.hd.size());
+    ++n_material_builds_;
     materials_.push_back(std::move(mat));
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
     ensure_layouts();
     return (uint32_t)materials_.size() - 1;
 }
@@ -316,7 +419,7 @@ uint32_t Context::add_dipole_material(const float *sigma_a, const float *sigmap_
     mat->rho.hd.assign(2, 0.f);
     mat->dev_rho.upload(mat->rho.hd.data(), mat->rho.hd.size());
     materials_.push_back(std::move(mat));
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
     return (uint32_t)materials_.size() - 1;
 }
 
@@ -364,7 +467,7 @@ std::unique_ptr<ImageTexture> build_imagemap(const mpss_imagemap &m) {
 uint32_t Context::add_imagemap(const mpss_imagemap &m) {
     std::lock_guard<std::mutex> g(mu_);
     textures_.push_back(build_imagemap(m));
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
     return (uint32_t)textures_.size() - 1;
 }
 
@@ -383,7 +486,7 @@ void Context::set_material_textures(uint32_t material, int albedo, int bump) {
     check(bump, true, "bumpmap");
     materials_[material]->albedo_tex = albedo;
     materials_[material]->bump_tex = bump;
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();  // (tessellation displaces the points along the bump map)
 }
 
 std::vector<const TexView *> Context::host_bump_views() const {
@@ -393,10 +496,10 @@ std::vector<const TexView *> Context::host_bump_views() const {
     return v;
 }
 
-const Material &Context::material(uint32_t id) const {
-    std::lock_guard<std::mutex> g(mu_);
-    if (id >= materials_.size()) throw Error(MPSS_ERR_INVALID, "unknown material id " + std::to_string(id));
-    return *materials_[id];
+void Context::require_fresh_irradiance(const char *who) const {
+    if (irradiance_stale_)
+        throw Error(MPSS_ERR_INVALID, std::string(who) + ": a material was updated since the last Preprocess; call "
+                                          "mpss_preprocess before rendering");
 }
 
 void Context::set_irradiance_points(int n, const float *p, const float *nrm, const float *E, const float *area) {
@@ -404,6 +507,7 @@ void Context::set_irradiance_points(int n, const float *p, const float *nrm, con
     std::lock_guard<std::mutex> g(mu_);
     quiesce_locked();  // no gather of the old octree may still be in flight or running
     build_octree_locked(n, p, nrm, E, area);
+    preprocessed_ = irradiance_stale_ = false;  // the caller's points and irradiance
 }
 
 // SubsurfaceOctreeNode::Insert / InitHierarchy over the points, the device copy and every
@@ -432,6 +536,7 @@ void Context::build_octree_locked(int n, const float *p, const float *nrm, const
         build_octree_device(n, dp ? dp : up.ptr, dn ? dn : un.ptr, dE ? dE : uE.ptr, uA.ptr, bmin, bmax, dev_octree_);
     }
     have_octree_ = true;
+    ++n_octree_builds_;
     dev_octree_.ensure_leaf_r2(max_error_);
     ensure_layouts();
 }

@@ -99,12 +99,25 @@ public:
     explicit Context(const mpss_config &cfg);
     ~Context();
     uint32_t add_layeredskin(const mpss_layeredskin &m);
+    // rebuilds material `id` in place (mpss_update_layeredskin): what add_layeredskin builds for m, under
+    // the same id, texture bindings and meshes; the Preprocess-derived irradiance goes stale
+    void update_layeredskin(uint32_t id, const mpss_layeredskin &m);
     uint32_t set_material_tables(const float *rd, uint32_t len, const float *rcp, const float *rho, uint32_t n_rho,
                                  const float *albedo, bool is_mc);
     // the single-dipole Rd of the dipolesubsurface integrator (dipole.h); usable with mo_batch
     uint32_t add_dipole_material(const float *sigma_a, const float *sigmap_s, float eta);
-    const Material &material(uint32_t id) const;
+    // copies under mu_ (a material may be rebuilt in place by update_layeredskin: no reference to one
+    // leaves the lock); sizes are always written, the buffers are nullable
+    void material_tables(uint32_t id, float *rd, uint32_t *len, float *rcp, float *rho, uint32_t *n_rho,
+                         float *total) const;
     void gather_info(uint32_t id, int *common_grid, float *rel_err, float *l1_err) const;
+    // the common grid the context built for material `id` and LDS layout near_field (mpss_get_common_grid;
+    // outputs as mpss_host_common_grid)
+    void common_grid(uint32_t id, int near_field, float *rows, uint32_t *n_rows, int32_t *bands, float *rg,
+                     float *u0lim, float *u1lim, float *u1start, uint32_t *row0, uint32_t *ubase, float *rel_err,
+                     float *l1_err, float *ua, float *hinv, int *ok) const;
+    // monotonic counts since creation: scene uploads, point-set builds, material table builds, octree builds
+    void build_counts(uint64_t counts[4]) const;
     void set_irradiance_points(int n, const float *p, const float *nrm, const float *E, const float *area);
     const DeviceOctree &octree() const;
     void export_octree(void *nodes, float *node_et, float *pt_hdr, float *pt_e, int32_t *pt_index);
@@ -145,11 +158,23 @@ public:
     // Cost probe for tile dealing: one camera ray through every pixel centre; per rect, the rays
     // that hit a BSSRDF surface (sss) and any mesh surface (surf). Synchronous.
     void tile_costs(int n, const int32_t *rects, int64_t *sss, int64_t *surf);
-    const std::vector<SurfacePoint> &surface_points() const { return points_; }
-    const std::vector<float> &irradiance() const { return irradiance_; }
+    // copies under mu_ (the point set is cached across Preprocess calls and dropped by mutators)
+    std::vector<SurfacePoint> surface_points() const {
+        std::lock_guard<std::mutex> g(mu_);
+        return points_;
+    }
+    std::vector<float> irradiance() const {
+        std::lock_guard<std::mutex> g(mu_);
+        return irradiance_;
+    }
     bool has_octree() const { return have_octree_; }
     mpss_render_stats render_stats();
     void reset_render_stats();
+    // which builder later material builds use for the common grids' per-knot scan (mpss_set_grid_builder)
+    void set_grid_builder(bool on_host) {
+        std::lock_guard<std::mutex> g(mu_);
+        grid_on_host_ = on_host;
+    }
     void set_instrumentation(bool timing, int counting) {
         std::lock_guard<std::mutex> g(mu_);
         cfg_.kernel_timing = timing;
@@ -159,6 +184,30 @@ public:
 private:
     void activate() const;
     void upload_scene();
+    // the materials' device records alone (d_materials_): all a material update changes of the scene
+    void upload_materials();
+    // the device scene is current: upload_scene when the scene changed, upload_materials when only a
+    // material was rebuilt (mu_ held)
+    void sync_scene_locked() {
+        if (scene_dirty_)
+            upload_scene();
+        else if (materials_dirty_)
+            upload_materials();
+    }
+    // anything tessellation or the Poisson point finder reads has changed (meshes, lights, camera, texture
+    // bindings, the material list): points the context built itself are found again by the next
+    // Preprocess; a caller's points (set_surface_points) stay, only their device copy is dropped (mu_ held)
+    void mark_scene_dirty_locked() {
+        scene_dirty_ = true;
+        invalidate_points_locked();
+    }
+    void invalidate_points_locked() {
+        if (points_src_ == PointsSrc::Built) points_src_ = PointsSrc::None;
+        pc_.valid = false;
+    }
+    std::unique_ptr<Material> build_layeredskin(const mpss_layeredskin &m);
+    // mpss_render_tile(s) / mpss_tile_costs after a material update and before the next Preprocess
+    void require_fresh_irradiance(const char *who) const;
     RenderScene render_scene() const;
     int first_bssrdf_material() const;
     // reference-sampler replay (mpss_config.sampler): floats per camera sample in the window tables,
@@ -172,8 +221,26 @@ private:
     void replay_window(RenderWorkspace *ws, const RenderScene &sc, int spp, int x0, int x1, int y0, int y1,
                        hipStream_t stream, bool all_values = false);
     SceneData scene_;
-    bool scene_dirty_ = true, have_points_ = false;
+    bool scene_dirty_ = true, materials_dirty_ = false;
+    // where points_ came from: the caller (set_surface_points / pointsfile) or a Preprocess of this
+    // context (tessellation or the Poisson finder, with points_seed_)
+    enum class PointsSrc { None, User, Built };
+    PointsSrc points_src_ = PointsSrc::None;
+    uint32_t points_seed_ = 0;
     std::vector<SurfacePoint> points_;
+    // Preprocess's arrays of points_ (position, normal, ray epsilon, material, uv; area on the host):
+    // they depend on the point set alone, so they are kept across Preprocess calls (pigment sweeps)
+    struct PointCache {
+        bool valid = false;
+        std::vector<float> p, nr, area;
+        DevBuf<float> dp, dn, de, duv;
+        DevBuf<uint32_t> dm;
+    } pc_;
+    // irradiance_ and the octree came from a Preprocess (not from set_irradiance_points), and a
+    // material was rebuilt since: renders are refused until the next Preprocess
+    bool preprocessed_ = false, irradiance_stale_ = false;
+    bool grid_on_host_ = false;  // (the GPU scan is the default: BASELINE.md section 3, "Pigment sweep")
+    uint64_t n_scene_uploads_ = 0, n_point_builds_ = 0, n_material_builds_ = 0, n_octree_builds_ = 0;
     std::vector<float> irradiance_;
     DevBuf<BvhNode> d_bvh_;
     DevBuf<BvhNode> d_bvh_thread_;  // threaded copy (interior offset = end of subtree), any-hit walks

@@ -67,7 +67,10 @@ struct DeviceProfile {
     float cg_rel_err[2][NB] = {};
     float cg_l1_err[2][NB] = {};
     // snake: deal the bands to groups in snake rounds instead of runs of adjacent reach (mo_band.h)
-    void upload(const float *table, int L, const float *rcp, bool snake = false);
+    // grid_host: the common grids' per-knot scan on the host (build_common_grid alone) instead of the GPU
+    // (scan_common_grid_gpu); the same grids bit for bit
+    void upload(const float *table, int L, const float *rcp, bool snake = false, bool grid_host = true);
+    bool grid_on_host = true;
     // (upload calls it with groups, set_rgb with rows 0..2 in every group; host table [NB][L])
     // lds_reserve: floats at the end of the LDS near field the grid's split leaves free
     // rgb: the slots are the rgbprofile's R, G, B (build_common_grid)
@@ -98,9 +101,20 @@ constexpr double kCgAbsTol = MPSS_CG_ABS_TOL;
 // float4 per row, group by group from cg.row0) and the per-band errors; true (cg.on) when some group
 // has rows. rgb: the slots are the rgbprofile's R, G, B, whose knots' errors are relative to the
 // largest of the three at that distance (the scale of FromRGB's outputs) instead of their own value.
+// pre: the per-knot scan's results from the GPU (below) instead of scanning here; the rest is the same code.
+struct CgScan {
+    std::vector<uint8_t> bad[kGroups][3];  // per group and row spacing H = 1, 2, 4: cells with a knot off by more than the bound
+    double peak[kGroups][4];               // each slot's largest |T|
+};
 bool build_common_grid(const float *tab, int L, const float *rcp, const BandGroups &groups, CommonGrid &cg,
                        std::vector<float4> &h, float rel_err[NB], float l1_err[NB], int near_field = 10236,
-                       int lds_reserve = 0, bool rgb = false);
+                       int lds_reserve = 0, bool rgb = false, const CgScan *pre = nullptr);
+// The part of build_common_grid that scales with 3 x L x bands, on the GPU (common_grid_gpu.hip): each
+// slot's peak |T| and the per-knot error test at H = 1, 2, 4 into the bad-cell maps, for both LDS layouts
+// (out[0]: 10236, out[1]: 5088) and all groups in one launch per stage. dev_tab: the [NB][L] table on the
+// device. False when no grid can be built (build_common_grid then declines by itself). Synchronous.
+bool scan_common_grid_gpu(const float *dev_tab, int L, const float *host_rcp, const BandGroups &slots,
+                          int lds_reserve, bool rgb, CgScan out[2]);
 
 // Choices of the sharded gather (mpss_config.mo_near_field / mo_work_stealing; count_noprune =
 // mpss_config.count_traversal == 2, instrumented passes only).

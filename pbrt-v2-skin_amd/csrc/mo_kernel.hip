@@ -502,7 +502,7 @@ void DeviceOctree::upload(const FlatOctree &t) {
     }
 }
 
-void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool snake) {
+void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool snake, bool grid_host) {
     // two zero floats after the last band: the sharded gather's read for "past the profile end"
     const size_t n = (size_t)NB * len;
     if (table.n != n + 2) table.alloc(n + 2);
@@ -515,6 +515,7 @@ void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool sn
     for (int c = 0; c < NB; ++c) host_rcp[c] = rcp_[c];
     groups = make_band_groups(rcp_, snake);
     rgb_refl.release();
+    grid_on_host = grid_host;
     build_common(tab, groups, 0, false);
 }
 
@@ -537,6 +538,11 @@ void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool sn
 #define MPSS_CG_MAX_ROWS_DEFAULT 49152
 #endif
 constexpr int kCgMaxRows = MPSS_CG_MAX_ROWS_DEFAULT;
+// The range search below tries at most 64 starts per group: the near field's end and the cells just
+// past the first 63 distinct bad fine knots. A table whose first accurate stretch begins after more
+// bad knots than that (a rough table, tests/test_common_grid.py) gets the best range among those 64
+// starts only -- still within the error bound (every served cell is checked), possibly shorter than
+// the best one; each start costs O(L / 64) argmax queries per row spacing.
 // (a diagnostic build, -DMPSS_DIAGNOSTICS, lets MPSS_CG_MAX_ROWS override the cap: row-cap experiments)
 static int cg_max_rows() {
 #ifdef MPSS_DIAGNOSTICS
@@ -548,7 +554,7 @@ static int cg_max_rows() {
 
 bool build_common_grid(const float *tab, int L, const float *host_rcp, const BandGroups &groups, CommonGrid &cg,
                        std::vector<float4> &h, float cg_rel_err[NB], float cg_l1_err[NB], int near_field,
-                       int lds_reserve, bool rgb) {
+                       int lds_reserve, bool rgb, const CgScan *pre) {
     cg = CommonGrid{};
     for (int g = 0; g < kGroups; ++g) {  // (one row per grid step unless the layout below says otherwise)
         cg.hinv[g] = 1.f;
@@ -669,7 +675,9 @@ bool build_common_grid(const float *tab, int L, const float *host_rcp, const Ban
         // grow with distance), a bad cell counting against it, within kCgMaxRows rows (+ one pad row).
         double peak[4] = {0.0, 0.0, 0.0, 0.0};  // each band's largest |T|
         for (int j = 0; j < 4; ++j)
-            if (groups.band[g][j] >= 0) {
+            if (pre) {  // (the GPU scan's, common_grid_gpu.hip: a maximum, the same bits in any order)
+                peak[j] = pre->peak[g][j];
+            } else if (groups.band[g][j] >= 0) {
                 const float *T = tab + (size_t)groups.band[g][j] * L;
                 for (int k = 0; k < L; ++k) peak[j] = std::max(peak[j], std::fabs((double)T[k]));
             }
@@ -709,7 +717,16 @@ bool build_common_grid(const float *tab, int L, const float *host_rcp, const Ban
         std::vector<uint8_t> bad[3];
         for (int hi = 0; hi < 3; ++hi) bad[hi].assign((size_t)ncell / kH[hi] + 2, 0);
         std::vector<double> fine_bad;  // u of the fine grid's bad knots (the candidate range starts)
-        for (int j = 0; j < 4; ++j) {
+        if (pre) {
+            // the three maps as the GPU scan left them (the same per-knot test, common_grid_gpu.hip). Only
+            // floor(u) of a bad fine knot is used below, and that is its cell in bad[0]: the set cells in
+            // ascending order stand for the sorted list, whatever order the GPU's threads ran in
+            for (int hi = 0; hi < 3; ++hi)
+                if (pre->bad[g][hi].size() == bad[hi].size()) bad[hi] = pre->bad[g][hi];
+            for (size_t m = 0; m < bad[0].size(); ++m)
+                if (bad[0][m]) fine_bad.push_back((double)m);
+        }
+        for (int j = 0; j < 4 && !pre; ++j) {
             if (groups.band[g][j] < 0) continue;
             for (int k = std::max(0, (int)std::floor((double)u0f * r[j]) - 1); k < L - 1; ++k) {
                 const double u = (double)k / r[j];
@@ -945,12 +962,19 @@ void DeviceProfile::build_common(const float *tab, const BandGroups &slots, int 
     // the two LDS layouts' grids side by side (host work: each builds its groups on threads of its own)
     std::vector<float4> hh, h;
     bool ok_half = false;
+    // the GPU builder: the per-knot scan of both layouts and all groups in one go, from the table
+    // already on the device (the rgbprofile's rows 0..2 are the first rows of the same table)
+    std::unique_ptr<CgScan[]> scan;
+    if (!grid_on_host) {
+        scan.reset(new CgScan[2]);
+        if (!scan_common_grid_gpu(table.ptr, L, host_rcp, slots, lds_reserve, rgb, scan.get())) scan.reset();
+    }
     std::thread half([&] {
         ok_half = build_common_grid(tab, L, host_rcp, slots, cg_half, hh, cg_rel_err[1], cg_l1_err[1], 5088,
-                                    lds_reserve, rgb);
+                                    lds_reserve, rgb, scan ? &scan[1] : nullptr);
     });
     const bool ok = build_common_grid(tab, L, host_rcp, slots, cg, h, cg_rel_err[0], cg_l1_err[0], 10236,
-                                      lds_reserve, rgb);
+                                      lds_reserve, rgb, scan ? &scan[0] : nullptr);
     half.join();
     if (ok_half) {
         ctab_half.upload(hh.data(), hh.size());

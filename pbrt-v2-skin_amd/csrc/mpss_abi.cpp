@@ -137,6 +137,24 @@ int mpss_add_layeredskin(mpss_ctx *c, const mpss_layeredskin *m, uint32_t *id) {
     });
 }
 
+int mpss_update_layeredskin(mpss_ctx *c, uint32_t id, const mpss_layeredskin *m) {
+    return guarded([&] {
+        require(c && m, "mpss_update_layeredskin: null argument");
+        require(m->desired_length >= 2 && m->desired_length <= 4096, "desiredlength out of range [2, 4096]");
+        require(m->nmperunit > 0.f, "nmperunit must be positive");
+        require(!m->show_irradiance_points || m->irradiance_point_size > 0.f,
+                "irradiancepointsize must be positive with showirradiancepoints");
+        reinterpret_cast<Context *>(c)->update_layeredskin(id, *m);
+    });
+}
+
+int mpss_build_counts(mpss_ctx *c, uint64_t counts[4]) {
+    return guarded([&] {
+        require(c && counts, "mpss_build_counts: null argument");
+        reinterpret_cast<Context *>(c)->build_counts(counts);
+    });
+}
+
 void mpss_imagemap_defaults(mpss_imagemap *t) {
     if (!t) return;
     memset(t, 0, sizeof(*t));
@@ -181,13 +199,7 @@ int mpss_get_material_tables(mpss_ctx *c, uint32_t id, float *rd, uint32_t *len,
                              uint32_t *n_rho, float *total) {
     return guarded([&] {
         require(c && len && n_rho, "mpss_get_material_tables: null argument");
-        const Material &m = reinterpret_cast<Context *>(c)->material(id);
-        *len = (uint32_t)m.profile.length;
-        *n_rho = (uint32_t)m.rho.hd.size();
-        if (rd) memcpy(rd, m.profile.table.data(), sizeof(float) * m.profile.table.size());
-        if (rcp) memcpy(rcp, m.profile.rcp, sizeof(float) * NB);
-        if (rho) memcpy(rho, m.rho.hd.data(), sizeof(float) * m.rho.hd.size());
-        if (total) memcpy(total, m.profile.total_reflectance, sizeof(float) * NB);
+        reinterpret_cast<Context *>(c)->material_tables(id, rd, len, rcp, rho, n_rho, total);
     });
 }
 
@@ -229,6 +241,17 @@ int mpss_host_common_grid(const float *table, uint32_t L, const float *rcp, int 
             if (rel_err) rel_err[c] = rel[c];
             if (l1_err) l1_err[c] = l1[c];
         }
+    });
+}
+
+int mpss_get_common_grid(mpss_ctx *c, uint32_t id, int near_field, float *rows, uint32_t *n_rows, int32_t *bands,
+                         float *rg, float *u0lim, float *u1lim, float *u1start, uint32_t *row0, uint32_t *ubase,
+                         float *rel_err, float *l1_err, float *ua, float *hinv, int *ok) {
+    return guarded([&] {
+        require(c && ok, "mpss_get_common_grid: null argument");
+        require(near_field == 10236 || near_field == 5088, "mpss_get_common_grid: near_field must be 10236 or 5088");
+        reinterpret_cast<Context *>(c)->common_grid(id, near_field, rows, n_rows, bands, rg, u0lim, u1lim, u1start, row0,
+                                                    ubase, rel_err, l1_err, ua, hinv, ok);
     });
 }
 
@@ -322,7 +345,7 @@ int mpss_set_surface_points(mpss_ctx *c, uint32_t n, const void *rec) {
 int mpss_get_surface_points(mpss_ctx *c, void *rec, uint32_t *n) {
     return guarded([&] {
         require(c && n, "mpss_get_surface_points: null argument");
-        const auto &v = reinterpret_cast<Context *>(c)->surface_points();
+        const auto v = reinterpret_cast<Context *>(c)->surface_points();
         *n = (uint32_t)v.size();
         if (rec) memcpy(rec, v.data(), sizeof(SurfacePoint) * v.size());
     });
@@ -347,7 +370,7 @@ int mpss_load_pointsfile(mpss_ctx *c, const char *path) {
 int mpss_save_pointsfile(mpss_ctx *c, const char *path) {
     return guarded([&] {
         require(c && path, "mpss_save_pointsfile: null argument");
-        const auto &v = reinterpret_cast<Context *>(c)->surface_points();
+        const auto v = reinterpret_cast<Context *>(c)->surface_points();
         FILE *f = fopen(path, "wb");
         if (!f) throw Error(MPSS_ERR_INVALID, std::string("mpss_save_pointsfile: cannot open ") + path);
         const size_t put = v.empty() ? 0 : fwrite(v.data(), sizeof(SurfacePoint), v.size(), f);
@@ -367,7 +390,7 @@ int mpss_replay_samples(mpss_ctx *c, int spp, float *out, uint64_t *n_floats, in
 int mpss_get_irradiance(mpss_ctx *c, float *E, uint32_t *n) {
     return guarded([&] {
         require(c && n, "mpss_get_irradiance: null argument");
-        const auto &v = reinterpret_cast<Context *>(c)->irradiance();
+        const auto v = reinterpret_cast<Context *>(c)->irradiance();
         *n = (uint32_t)(v.size() / NB);
         if (E) memcpy(E, v.data(), sizeof(float) * v.size());
     });
@@ -384,6 +407,13 @@ int mpss_set_instrumentation(mpss_ctx *c, int timing, int counting) {
     return guarded([&] {
         require(c, "mpss_set_instrumentation: null ctx");
         reinterpret_cast<Context *>(c)->set_instrumentation(timing != 0, counting);
+    });
+}
+
+int mpss_set_grid_builder(mpss_ctx *c, int on_host) {
+    return guarded([&] {
+        require(c, "mpss_set_grid_builder: null ctx");
+        reinterpret_cast<Context *>(c)->set_grid_builder(on_host != 0);
     });
 }
 

@@ -49,7 +49,7 @@ void Context::add_mesh(uint32_t nv, const float *P, const float *N, const float 
     m.reverse_orientation = reverse;
     m.swaps_handedness = det3(o2w) < 0.f;  // Transform::SwapsHandedness
     scene_.meshes.push_back(std::move(m));
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
 }
 
 void Context::add_sphere_light(const float *c, float r, const float *Lemit, int nsamples) {
@@ -63,7 +63,7 @@ void Context::add_sphere_light(const float *c, float r, const float *Lemit, int 
     memcpy(l.Lemit, Lemit, sizeof(l.Lemit));
     l.nsamples = cfg_.quick_render ? std::max(1, nsamples / 4) : nsamples;  // CreateDiffuseAreaLight
     scene_.lights.push_back(l);
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
 }
 
 // CreateInfiniteLight + the InfiniteAreaLight ctor without a map (lights/infinite.cpp:66-90,
@@ -100,7 +100,7 @@ void Context::add_infinite_light(const float *L, int nsamples, const float *l2w,
         }
     l.nsamples = cfg_.quick_render ? std::max(1, nsamples / 4) : nsamples;  // CreateInfiniteLight
     scene_.lights.push_back(std::move(l));
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
 }
 
 void Context::set_camera(const float *r2c, const float *c2w, int xres, int yres) {
@@ -110,7 +110,7 @@ void Context::set_camera(const float *r2c, const float *c2w, int xres, int yres)
     memcpy(scene_.camera.camera_to_world, c2w, sizeof(float) * 16);
     scene_.camera.xres = xres;
     scene_.camera.yres = yres;
-    scene_dirty_ = true;
+    mark_scene_dirty_locked();
 }
 
 void Context::upload_scene() {
@@ -237,10 +237,21 @@ void Context::upload_scene() {
     d_lights_.upload(rl.data(), rl.size());
     replay_k_ = replay_off;
     ++scene_gen_;  // the workspaces' replay cursors belong to the old scene
-    std::vector<RenderMaterial> rmat;
+    ++n_scene_uploads_;
     if (!d_lut_.ptr) d_lut_.upload(ewa_weight_lut(), kEwaLut);
     for (auto &t : textures_)
         if (!t->dev.ptr) t->dev.upload(t->py.data.data(), t->py.data.size());
+    upload_materials();
+    scene_dirty_ = false;
+}
+
+// The RenderMaterial records (d_materials_) from materials_: the whole of the device scene that a
+// material's parameters reach. The textures they view are on the device already (upload_scene: binding
+// or adding one marks the scene dirty).
+void Context::upload_materials() {
+    activate();
+    quiesce_locked();  // in-flight renders read d_materials_
+    std::vector<RenderMaterial> rmat;
     for (const auto &mp : materials_) {
         const Material &m = *mp;
         RenderMaterial r{};
@@ -287,7 +298,7 @@ void Context::upload_scene() {
         rmat.push_back(r);
     }
     d_materials_.upload(rmat.data(), rmat.size());
-    scene_dirty_ = false;
+    materials_dirty_ = false;
 }
 
 RenderScene Context::render_scene() const {
@@ -325,7 +336,8 @@ RenderScene Context::render_scene() const {
 void Context::set_surface_points(uint32_t n, const SurfacePoint *pts) {
     std::lock_guard<std::mutex> g(mu_);
     points_.assign(pts, pts + n);
-    have_points_ = n > 0;
+    points_src_ = n > 0 ? PointsSrc::User : PointsSrc::None;
+    pc_.valid = false;
 }
 
 // TessellateSurfacePointsRenderer's point set on the GPU (tess_kernel): per mesh a counting pass,
@@ -382,19 +394,36 @@ void Context::preprocess(uint32_t seed) {
     activate();
     std::lock_guard<std::mutex> g(mu_);
     quiesce_locked();  // no render of the previous octree may still be in flight or running
-    if (scene_dirty_) upload_scene();
+    sync_scene_locked();
+    // (on every regular way out: the irradiance and octree, or their absence, are this Preprocess's)
+    auto fresh = [&] {
+        preprocessed_ = true;
+        irradiance_stale_ = false;
+    };
     if (scene_.lights.empty()) {  // "if (scene->lights.size() == 0) return;" -> no octree, no SSS
         have_octree_ = false;
         irradiance_.clear();
+        fresh();
         return;
     }
-    if (!have_points_) {
+    // The point set depends on the meshes, min_sample_distance, incenter, the bump maps bound to the
+    // meshes' materials (tessellation), and on the scene bounds with the area lights, the camera
+    // position and the seed (Poisson finder) -- not on a material's tables: points built by an earlier
+    // Preprocess are kept until one of those changes (mark_scene_dirty_locked), so a Preprocess after a
+    // material update runs the irradiance kernel and the octree build only.
+    if (points_src_ == PointsSrc::None ||
+        (points_src_ == PointsSrc::Built && cfg_.use_poisson_point_finder && seed != points_seed_)) {
+        pc_.valid = false;
+        points_src_ = PointsSrc::None;
         if (cfg_.use_poisson_point_finder)
             find_poisson_points(seed);
         else if (cfg_.tessellate_on_host)
             tessellate_surface_points(scene_, min_dist_, cfg_.incenter != 0, points_, 0, host_bump_views().data());
         else
             tessellate_on_gpu();
+        points_src_ = PointsSrc::Built;
+        points_seed_ = seed;
+        ++n_point_builds_;
     }
     const int n = (int)points_.size();
     if (n == 0) {
@@ -404,28 +433,37 @@ void Context::preprocess(uint32_t seed) {
                         "subsurface scattering\n");
         have_octree_ = false;
         irradiance_.clear();
+        fresh();
         return;
     }
-    std::vector<float> p(3 * (size_t)n), nr(3 * (size_t)n), eps(n);
-    std::vector<uint32_t> mat(n);
-    std::vector<float> uv(2 * (size_t)n);
-    for (int i = 0; i < n; ++i) {
-        uv[2 * (size_t)i] = points_[i].u;
-        uv[2 * (size_t)i + 1] = points_[i].v;
-        for (int k = 0; k < 3; ++k) {
-            p[3 * (size_t)i + k] = points_[i].p[k];
-            nr[3 * (size_t)i + k] = points_[i].n[k];
+    if (!pc_.valid) {  // the points' arrays, host and device, until the point set changes
+        std::vector<float> eps(n), uv(2 * (size_t)n);
+        std::vector<uint32_t> mat(n);
+        pc_.p.resize(3 * (size_t)n);
+        pc_.nr.resize(3 * (size_t)n);
+        pc_.area.resize(n);
+        for (int i = 0; i < n; ++i) {
+            uv[2 * (size_t)i] = points_[i].u;
+            uv[2 * (size_t)i + 1] = points_[i].v;
+            for (int k = 0; k < 3; ++k) {
+                pc_.p[3 * (size_t)i + k] = points_[i].p[k];
+                pc_.nr[3 * (size_t)i + k] = points_[i].n[k];
+            }
+            eps[i] = points_[i].ray_eps;
+            mat[i] = points_[i].material;
+            pc_.area[i] = points_[i].area;
         }
-        eps[i] = points_[i].ray_eps;
-        mat[i] = points_[i].material;
+        pc_.duv.upload(uv.data(), uv.size());
+        pc_.dp.upload(pc_.p.data(), pc_.p.size());
+        pc_.dn.upload(pc_.nr.data(), pc_.nr.size());
+        pc_.de.upload(eps.data(), eps.size());
+        pc_.dm.upload(mat.data(), mat.size());
+        pc_.valid = true;
     }
-    DevBuf<float> dp, dn, de, dE, duv;
-    DevBuf<uint32_t> dm;
-    duv.upload(uv.data(), uv.size());
-    dp.upload(p.data(), p.size());
-    dn.upload(nr.data(), nr.size());
-    de.upload(eps.data(), eps.size());
-    dm.upload(mat.data(), mat.size());
+    const std::vector<float> &p = pc_.p, &nr = pc_.nr, &area = pc_.area;
+    const DevBuf<float> &dp = pc_.dp, &dn = pc_.dn, &de = pc_.de, &duv = pc_.duv;
+    const DevBuf<uint32_t> &dm = pc_.dm;
+    DevBuf<float> dE;
     dE.alloc((size_t)n * NB);
     const RenderScene sc = render_scene();
     if (cfg_.show_irradiance_points) {  // IrradianceTask: red points instead of irradiance
@@ -455,11 +493,10 @@ void Context::preprocess(uint32_t seed) {
         irradiance_.resize((size_t)n * NB);
         MPSS_HIP(hipMemcpy(irradiance_.data(), dE.ptr, sizeof(float) * irradiance_.size(), hipMemcpyDeviceToHost));
     }
-    std::vector<float> area(n);
-    for (int i = 0; i < n; ++i) area[i] = points_[i].area;
     const bool e_on_device = !cfg_.show_irradiance_points;  // dE holds the irradiance kernel's output
     build_octree_locked(n, p.data(), nr.data(), irradiance_.data(), area.data(), dp.ptr, dn.ptr,
                         e_on_device ? dE.ptr : nullptr);
+    fresh();
 }
 
 // FindPoissonPointDistribution -> SurfacePointsRenderer::Render (renderers/surfacepoints.cpp:115-150)
@@ -469,7 +506,7 @@ void Context::preprocess(uint32_t seed) {
 // accepted point lies within minDist (PoissonCheck: DistanceSquared < minDist^2; the reference's
 // octree lookup finds exactly those), until maxFails candidates in a row fail.
 void Context::find_poisson_points(uint32_t seed) {
-    if (scene_dirty_) upload_scene();
+    sync_scene_locked();
     activate();
     // scene->WorldBound(): every triangle and every area-light sphere
     float lo[3], hi[3];
@@ -630,7 +667,7 @@ void Context::replay_samples(int spp, float *out, uint64_t *n_floats, int *k) {
     activate();
     std::unique_lock<std::mutex> lk(mu_);
     if (cfg_.sampler != MPSS_SAMPLER_REFERENCE) throw Error(MPSS_ERR_INVALID, "replay_samples: the context uses the hash sampler");
-    if (scene_dirty_) upload_scene();
+    sync_scene_locked();
     const int W = scene_.camera.xres, H = scene_.camera.yres;
     if (W <= 0) throw Error(MPSS_ERR_INVALID, "replay_samples: no camera");
     spp = round_up_pow2(spp);
@@ -662,7 +699,8 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
                            hipStream_t stream) {
     activate();
     std::unique_lock<std::mutex> lk(mu_);
-    if (scene_dirty_) upload_scene();
+    require_fresh_irradiance("render_tile");
+    sync_scene_locked();
     const int W = scene_.camera.xres, H = scene_.camera.yres;
     if (W <= 0) throw Error(MPSS_ERR_INVALID, "render_tile: no camera");
     if (spp < 1 || spp > 65535) throw Error(MPSS_ERR_INVALID, "render_tile: spp must be in [1, 65535]");
@@ -979,7 +1017,8 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
 void Context::tile_costs(int n, const int32_t *rects, int64_t *sss, int64_t *surf) {
     activate();
     std::lock_guard<std::mutex> g(mu_);
-    if (scene_dirty_) upload_scene();
+    require_fresh_irradiance("tile_costs");
+    sync_scene_locked();
     const int W = scene_.camera.xres, H = scene_.camera.yres;
     if (W <= 0) throw Error(MPSS_ERR_INVALID, "tile_costs: no camera");
     RenderScene sc = render_scene();

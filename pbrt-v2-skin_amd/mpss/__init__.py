@@ -98,6 +98,10 @@ _sig("mpss_create", C.c_int, [C.POINTER(Config), C.POINTER(vp)])
 _sig("mpss_destroy", None, [vp])
 _sig("mpss_layeredskin_defaults", None, [C.POINTER(LayeredSkin)])
 _sig("mpss_add_layeredskin", C.c_int, [vp, C.POINTER(LayeredSkin), u32p])
+_sig("mpss_update_layeredskin", C.c_int, [vp, u32, C.POINTER(LayeredSkin)])
+_sig("mpss_build_counts", C.c_int, [vp, C.POINTER(C.c_uint64)])
+_sig("mpss_get_common_grid", C.c_int, [vp, u32, C.c_int, vp, u32p] + [vp] * 11 + [C.POINTER(C.c_int)])
+_sig("mpss_set_grid_builder", C.c_int, [vp, C.c_int])
 _sig("mpss_set_material_tables", C.c_int, [vp, f32p, u32, f32p, f32p, u32, vp, C.c_int, u32p])
 _sig("mpss_add_dipole_material", C.c_int, [vp, f32p, f32p, C.c_float, u32p])
 _sig("mpss_host_dipole_rd", C.c_int, [f32p, f32p, C.c_float, u32, vp, vp, vp])
@@ -373,6 +377,42 @@ class Context:
         mid = C.c_uint32()
         check(_lib.mpss_add_layeredskin(self.h, C.byref(skin), C.byref(mid)))
         return mid.value
+
+    def update_layeredskin(self, mid, skin):
+        """mpss_update_layeredskin: material `mid` rebuilt in place for `skin` (id, texture bindings and
+        meshes kept). Run preprocess() again before the next render."""
+        check(_lib.mpss_update_layeredskin(self.h, mid, C.byref(skin)))
+
+    def build_counts(self):
+        """mpss_build_counts: monotonic counts of scene uploads, point-set builds, material table
+        builds and octree builds since the context was created."""
+        c = (C.c_uint64 * 4)()
+        check(_lib.mpss_build_counts(self.h, c))
+        return dict(scene_uploads=int(c[0]), point_builds=int(c[1]), material_builds=int(c[2]),
+                    octree_builds=int(c[3]))
+
+    def set_grid_builder(self, on_host=True):
+        """mpss_set_grid_builder: the common grids' per-knot scan of later material builds on the host
+        (True) or on the GPU (False); the same grids either way."""
+        check(_lib.mpss_set_grid_builder(self.h, int(bool(on_host))))
+
+    def common_grid(self, mid, near_field=5088):
+        """mpss_get_common_grid: the grid the context built for material `mid` and the LDS layout
+        near_field, as the dict of mpss.host_common_grid."""
+        n = C.c_uint32(0)
+        ok = C.c_int()
+        check(_lib.mpss_get_common_grid(self.h, mid, int(near_field), None, C.byref(n), *([None] * 11), C.byref(ok)))
+        out = dict(rows=np.zeros((n.value, 8), np.float32), bands=np.zeros((8, 4), np.int32),
+                   rg=np.zeros(8, np.float32), u0lim=np.zeros(8, np.float32), u1lim=np.zeros(8, np.float32),
+                   u1start=np.zeros(8, np.float32), row0=np.zeros(8, np.uint32), ubase=np.zeros(8, np.uint32),
+                   rel_err=np.zeros(NB, np.float32), l1_err=np.zeros(NB, np.float32), ua=np.zeros(8, np.float32),
+                   hinv=np.zeros(8, np.float32))
+        check(_lib.mpss_get_common_grid(self.h, mid, int(near_field), out["rows"].ctypes.data, C.byref(n),
+                                        *[out[k].ctypes.data for k in ("bands", "rg", "u0lim", "u1lim", "u1start",
+                                                                       "row0", "ubase", "rel_err", "l1_err", "ua",
+                                                                       "hinv")], C.byref(ok)))
+        out["ok"] = bool(ok.value)
+        return out
 
     def set_material_tables(self, table, rcp, rho_hd, albedo=None, is_mc=False):
         table = np.ascontiguousarray(table, np.float32)

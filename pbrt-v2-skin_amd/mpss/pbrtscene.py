@@ -487,17 +487,31 @@ def infinite_texels(li):
     return imageio.read_image(li["mapname"])
 
 
-def build_context(sc, **cfg_kw):
-    """Create an mpss.Context holding the scene (materials, meshes, lights, camera)."""
+def skin_struct(m):
+    """The mpss_layeredskin of one of a Scene's material dicts (its texture bindings aside)."""
+    import mpss
+    kw = {k: v for k, v in m.items() if k not in ("Kr", "Kt", "albedo", "albedo_tex", "bump_tex")}
+    for k in ("Kr", "Kt", "albedo"):
+        if k in m:
+            kw[k] = mpss.host_from_rgb(m[k])
+    return mpss.default_skin(**kw)
+
+
+def build_context(sc, timings=None, grid_on_host=None, **cfg_kw):
+    """Create an mpss.Context holding the scene (materials, meshes, lights, camera). timings: a dict
+    that receives material_s, the seconds spent building the materials' tables. grid_on_host: the
+    common-grid builder (Context.set_grid_builder), None for the library's default."""
+    import time
     import mpss
     ctx = mpss.Context(**integrator_config(sc, **cfg_kw))
+    if grid_on_host is not None:
+        ctx.set_grid_builder(grid_on_host)
     mids = []
+    t0 = time.perf_counter()
     for m in sc.materials:
-        kw = {k: v for k, v in m.items() if k not in ("Kr", "Kt", "albedo", "albedo_tex", "bump_tex")}
-        for k in ("Kr", "Kt", "albedo"):
-            if k in m:
-                kw[k] = mpss.host_from_rgb(m[k])
-        mids.append(ctx.add_layeredskin(mpss.default_skin(**kw)))
+        mids.append(ctx.add_layeredskin(skin_struct(m)))
+    if timings is not None:
+        timings["material_s"] = time.perf_counter() - t0
     for m, mid in zip(sc.materials, mids):
         if m.get("albedo_tex") is not None or m.get("bump_tex") is not None:
             alb = ctx.add_imagemap(**m["albedo_tex"]) if m.get("albedo_tex") is not None else -1
