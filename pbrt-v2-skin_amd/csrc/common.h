@@ -6,10 +6,9 @@
 #include <string>
 #include <stdexcept>
 
-namespace mpss {
+#include "common_grid_types.h"  // NB, ROW
 
-constexpr int NB = 30;      // nSpectralSamples (reference src/core/spectrum.h:46)
-constexpr int ROW = 32;     // padded spectral row: 30 bands + 2 pad lanes, 128 B per row
+namespace mpss {
 
 struct Error : std::runtime_error {
     int code;

@@ -50,6 +50,7 @@ struct DeviceOctree {
 void build_octree_device(int n, const float *P, const float *N, const float *E, const float *A, const float bmin[3],
                          const float bmax[3], DeviceOctree &t);
 
+// (upload, set_rgb and build_common: device_profile.cpp)
 struct DeviceProfile {
     DevBuf<float> table;  // [NB][L] channel-major + 2 trailing zeros
     DevBuf<float> rcp;    // [NB]
@@ -57,7 +58,7 @@ struct DeviceProfile {
     int L = 0;
     float host_rcp[NB];
     BandGroups groups{};   // band -> XCD group assignment for this profile
-    // The common grid of each band group (mo_band.h CommonGrid), built by upload() for each LDS layout
+    // The common grid of each band group (common_grid_types.h CommonGrid), built by upload() for each LDS layout
     // (the 10236-entry near field: cg; the 5088-entry one, the default: cg_half): ctab / ctab_half hold
     // the groups' pair rows (two float4 per row); on = 1 when some group has an accurate row range.
     DevBuf<float4> ctab, ctab_half;
@@ -66,14 +67,14 @@ struct DeviceProfile {
     // |R - T| over those knots / the sum of |T| over the table ([0]: 10236 layout, [1]: 5088)
     float cg_rel_err[2][NB] = {};
     float cg_l1_err[2][NB] = {};
-    // snake: deal the bands to groups in snake rounds instead of runs of adjacent reach (mo_band.h)
-    // grid_host: the common grids' per-knot scan on the host (build_common_grid alone) instead of the GPU
-    // (scan_common_grid_gpu); the same grids bit for bit
+    // snake: deal the bands to groups in snake rounds instead of runs of adjacent reach (common_grid_types.h)
+    // grid_host: the common grids' per-knot scan on the host (common_grid.h build_common_grid alone) instead
+    // of the GPU (scan_common_grid_gpu); the same grids bit for bit
     void upload(const float *table, int L, const float *rcp, bool snake = false, bool grid_host = true);
     bool grid_on_host = true;
     // (upload calls it with groups, set_rgb with rows 0..2 in every group; host table [NB][L])
     // lds_reserve: floats at the end of the LDS near field the grid's split leaves free
-    // rgb: the slots are the rgbprofile's R, G, B (build_common_grid)
+    // rgb: the slots are the rgbprofile's R, G, B (common_grid.h build_common_grid)
     void build_common(const float *table, const BandGroups &slots, int lds_reserve, bool rgb);
     // rgbprofile material: rows 0..2 of the table are its R, G, B profiles; the sharded gather looks
     // up those three for every group and converts them with FromRGB (rgb_refl: the device copy of
@@ -81,40 +82,6 @@ struct DeviceProfile {
     DevBuf<float> rgb_refl;
     void set_rgb(const float *table);
 };
-
-// The common grid's bound on the resampling error of a lookup: kCgRelTol of the band's own value
-// there, or kCgAbsTol of the band's peak where that is larger (the far tails, whose values fall to
-// 1e-11 of the peak and carry under 1 % of a band's mass on C2's profile: there the bound is
-// absolute). DeviceProfile::build_common; a group row (cell) holding a knot off by more is flagged and
-// its lanes read the exact tables. The floor is chosen on the full C2 frame against the oracle, same
-// box (profiles/r06_grid_ab.txt, rows H steps apart with flagged cells): 1e-13: gather 43.4 ms,
-// unfloored image error 3.3e-5; 1e-14: 43.9 ms, 1.5e-6; 1e-15: 45.1 ms, 1.1e-6 -- the worst values at
-// 1e-16 of the frame's peak, far below the film's resolution (round 4, one stretch of rows per group,
-// profiles/r04p_abstol.txt: none 60.4 ms, 1.1e-6; 1e-13 48.6 ms, 4.3e-6; 1e-10 47.1 ms, 9.0e-5).
-constexpr double kCgRelTol = 2e-6;
-#ifndef MPSS_CG_ABS_TOL  // (A/B builds of the floor only)
-#define MPSS_CG_ABS_TOL 1e-14
-#endif
-constexpr double kCgAbsTol = MPSS_CG_ABS_TOL;
-
-// The host half of DeviceProfile::build_common: the layout (cg, without tab), the pair rows h (two
-// float4 per row, group by group from cg.row0) and the per-band errors; true (cg.on) when some group
-// has rows. rgb: the slots are the rgbprofile's R, G, B, whose knots' errors are relative to the
-// largest of the three at that distance (the scale of FromRGB's outputs) instead of their own value.
-// pre: the per-knot scan's results from the GPU (below) instead of scanning here; the rest is the same code.
-struct CgScan {
-    std::vector<uint8_t> bad[kGroups][3];  // per group and row spacing H = 1, 2, 4: cells with a knot off by more than the bound
-    double peak[kGroups][4];               // each slot's largest |T|
-};
-bool build_common_grid(const float *tab, int L, const float *rcp, const BandGroups &groups, CommonGrid &cg,
-                       std::vector<float4> &h, float rel_err[NB], float l1_err[NB], int near_field = 10236,
-                       int lds_reserve = 0, bool rgb = false, const CgScan *pre = nullptr);
-// The part of build_common_grid that scales with 3 x L x bands, on the GPU (common_grid_gpu.hip): each
-// slot's peak |T| and the per-knot error test at H = 1, 2, 4 into the bad-cell maps, for both LDS layouts
-// (out[0]: 10236, out[1]: 5088) and all groups in one launch per stage. dev_tab: the [NB][L] table on the
-// device. False when no grid can be built (build_common_grid then declines by itself). Synchronous.
-bool scan_common_grid_gpu(const float *dev_tab, int L, const float *host_rcp, const BandGroups &slots,
-                          int lds_reserve, bool rgb, CgScan out[2]);
 
 // Choices of the sharded gather (mpss_config.mo_near_field / mo_work_stealing; count_noprune =
 // mpss_config.count_traversal == 2, instrumented passes only).

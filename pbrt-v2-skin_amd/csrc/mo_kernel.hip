@@ -31,9 +31,7 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 namespace mpss {
@@ -500,494 +498,6 @@ void DeviceOctree::upload(const FlatOctree &t) {
         bmin[k] = t.bmin[k];
         bmax[k] = t.bmax[k];
     }
-}
-
-void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool snake, bool grid_host) {
-    // two zero floats after the last band: the sharded gather's read for "past the profile end"
-    const size_t n = (size_t)NB * len;
-    if (table.n != n + 2) table.alloc(n + 2);
-    MPSS_HIP(hipMemcpy(table.ptr, tab, n * sizeof(float), hipMemcpyHostToDevice));
-    MPSS_HIP(hipMemset(table.ptr + n, 0, 2 * sizeof(float)));
-    rcp.upload(rcp_, NB);
-    L = len;
-    rcp_min = rcp_[0];
-    for (int c = 1; c < NB; ++c) rcp_min = rcp_[c] < rcp_min ? rcp_[c] : rcp_min;
-    for (int c = 0; c < NB; ++c) host_rcp[c] = rcp_[c];
-    groups = make_band_groups(rcp_, snake);
-    rgb_refl.release();
-    grid_on_host = grid_host;
-    build_common(tab, groups, 0, false);
-}
-
-// The common grid (mo_band.h CommonGrid), on the host from the band tables:
-//   * group g's grid is its longest-reach band's own (rg = the smallest rcp), u = d2 * rg;
-//   * the LDS budget of the wide kernel (4 x 10239 floats) is split so that every slot's exact near
-//     field ends at the same distance: klim_j ~ K0 * rcp_j / rg, and u0lim = min_j klim_j rg / rcp_j
-//     (less a 2^-18 margin) guarantees s_j = fl(d2 rcp_j) < klim_j for every lane with u < u0lim;
-//   * R_j(u) = band j's lerp at f = u * rcp_j / rg in double (its last segment continued one row past
-//     its end, 0 after); on the group rows a lane computes (1 - t) R_j(u0) + t R_j(u0 + 1);
-//   * the row range: the far path reads R where the band gather reads T, both piecewise linear, so the
-//     largest error lies on a knot of one of the two grids, and at the group grid's knots R is T's own
-//     lerp; every band knot s >= u0lim rcp_j / rg - 1 is compared (R's lerp at u = s rg / rcp_j against
-//     T[s]), and the rows end one cell before the first knot whose error exceeds kCgRelTol of |T[s]|
-//     (unfloored: a zero or a sign change ends it) -- past it every lookup reads the exact tables; for
-//     the rgbprofile's R, G, B (rgb) of the largest of the three at that distance instead of |T[s]|;
-//   * at most kCgMaxRows rows per group (32 B each: a group's rows stay well inside its XCD's 4 MB L2);
-//   * tau_j = the smallest float d2 with fl(d2 * rcp_j) >= L - 1 (sampleProfile's range test).
-#ifndef MPSS_CG_MAX_ROWS_DEFAULT  // (A/B builds of the cap only)
-#define MPSS_CG_MAX_ROWS_DEFAULT 49152
-#endif
-constexpr int kCgMaxRows = MPSS_CG_MAX_ROWS_DEFAULT;
-// The range search below tries at most 64 starts per group: the near field's end and the cells just
-// past the first 63 distinct bad fine knots. A table whose first accurate stretch begins after more
-// bad knots than that (a rough table, tests/test_common_grid.py) gets the best range among those 64
-// starts only -- still within the error bound (every served cell is checked), possibly shorter than
-// the best one; each start costs O(L / 64) argmax queries per row spacing.
-// (a diagnostic build, -DMPSS_DIAGNOSTICS, lets MPSS_CG_MAX_ROWS override the cap: row-cap experiments)
-static int cg_max_rows() {
-#ifdef MPSS_DIAGNOSTICS
-    const char *e = getenv("MPSS_CG_MAX_ROWS");
-    if (e && atoi(e) > 0) return atoi(e);
-#endif
-    return kCgMaxRows;
-}
-
-bool build_common_grid(const float *tab, int L, const float *host_rcp, const BandGroups &groups, CommonGrid &cg,
-                       std::vector<float4> &h, float cg_rel_err[NB], float cg_l1_err[NB], int near_field,
-                       int lds_reserve, bool rgb, const CgScan *pre) {
-    cg = CommonGrid{};
-    for (int g = 0; g < kGroups; ++g) {  // (one row per grid step unless the layout below says otherwise)
-        cg.hinv[g] = 1.f;
-        cg.hc[g] = 0.f;
-        cg.ua[g] = (float)L;
-    }
-    h.clear();
-    for (int c = 0; c < NB; ++c) cg_rel_err[c] = cg_l1_err[c] = 0.f;
-    const int kLdsFloats = 4 * (near_field + 3) - lds_reserve;
-    if (L < 4) return false;
-    for (int g = 0; g < kGroups; ++g)
-        for (int j = 0; j < 4; ++j) {
-            const int c = groups.band[g][j];
-            if (c >= 0 && (!(host_rcp[c] > 0.f) || !std::isfinite(host_rcp[c])))
-                return false;  // no uniform grid to resample
-        }
-    // The groups are independent (their own slots, LDS split, rows and errors): each is built on its
-    // own thread into its own row block, then the blocks are laid out in group order. (For the
-    // rgbprofile all groups hold the same three slots: one group is built and copied.)
-    std::vector<float4> hg[kGroups];
-    float relg[kGroups][4] = {}, l1g[kGroups][4] = {};
-    bool anyg[kGroups] = {}, failg[kGroups] = {};
-    auto build_group = [&](int g) {
-        std::vector<float4> &h = hg[g];
-        float rg = INFINITY;
-        int nfull = 0;
-        for (int j = 0; j < 4; ++j)
-            if (groups.band[g][j] >= 0) {
-                rg = std::min(rg, host_rcp[groups.band[g][j]]);
-                ++nfull;
-            }
-        if (nfull == 0) {  // an unused group: no wave ever walks it
-            for (int j = 0; j < 4; ++j) {
-                cg.lrow[g][j] = (uint32_t)(2 * j);
-                cg.lcnt[g][j] = 2;
-            }
-            return;
-        }
-        double r[4] = {0.0, 0.0, 0.0, 0.0}, rsum = 0.0;
-        for (int j = 0; j < 4; ++j)
-            if (groups.band[g][j] >= 0) {
-                r[j] = (double)host_rcp[groups.band[g][j]] / (double)rg;
-                rsum += r[j];
-            }
-        // near-field split: sum_j (klim_j + 1) <= kLdsFloats (empty slots: 2 zero floats)
-        int K0 = (int)std::floor((kLdsFloats - 3.0 * nfull - 2.0 * (4 - nfull) - 8.0) / rsum);
-        int klim[4], total;
-        for (;;) {
-            total = 0;
-            for (int j = 0; j < 4; ++j) {
-                if (groups.band[g][j] < 0) {
-                    klim[j] = 1;
-                } else {
-                    const double want = std::ceil((double)K0 * r[j] * (1.0 + 1e-6)) + 1.0;
-                    klim[j] = (int)std::min<double>(want, (double)(L - 2));
-                }
-                total += klim[j] + 1;
-            }
-            if (total <= kLdsFloats || K0 <= 1) break;
-            --K0;
-        }
-        if (total > kLdsFloats) {
-            failg[g] = true;
-            return;
-        }
-        uint32_t off = 0;
-        double u0 = INFINITY;
-        for (int j = 0; j < 4; ++j) {
-            cg.lrow[g][j] = off;
-            cg.lcnt[g][j] = klim[j] + 1;
-            off += (uint32_t)(klim[j] + 1);
-            if (groups.band[g][j] >= 0) u0 = std::min(u0, (double)klim[j] / r[j] * (1.0 - 0x1p-18));
-        }
-        float u0f = (float)u0;
-        if ((double)u0f > u0) u0f = std::nextafter(u0f, 0.f);
-        cg.u0lim[g] = u0f;
-        cg.rg[g] = rg;
-        // a leaf is LDS-only when every lane's u < u0lim: leaf_r2 * rg below u0lim, with a 1e-5 margin
-        // for the rounding of the lanes' d2 (as the band gather's lds_r2_lim)
-        cg.lds_r2[g] = (float)((double)u0f / ((double)rg * 1.00001));
-        for (int j = 0; j < 4; ++j) {
-            const int c = groups.band[g][j];
-            if (c < 0) {
-                cg.tau[g][j] = INFINITY;  // (its sum is never stored)
-                continue;
-            }
-            const float rc = host_rcp[c];
-            const float endf = (float)(L - 1);
-            float x = (float)((double)(L - 1) / (double)rc);
-            auto past = [&](float d2) {
-                volatile float f = d2 * rc;  // the float product of sampleProfile (multipole.cpp:63)
-                return f >= endf;
-            };
-            while (x > 0.f && past(x)) x = std::nextafter(x, 0.f);
-            while (!past(x)) x = std::nextafter(x, INFINITY);
-            cg.tau[g][j] = x;
-        }
-        // R_j(u): band j on the group grid (double lerp, rounded once)
-        auto R = [&](int j, int64_t u) -> float {
-            const int c = groups.band[g][j];
-            if (c < 0 || u >= (int64_t)L) return 0.f;
-            const double f = (double)u * r[j];
-            if (f - r[j] > (double)(L - 1)) return 0.f;  // past the row after the band's end
-            const int sidx = std::min((int)std::floor(f), L - 2);
-            const double t = f - sidx;
-            const float *T = tab + (size_t)c * L;
-            return (float)((1.0 - t) * (double)T[sidx] + t * (double)T[sidx + 1]);
-        };
-        // The row layout. Rows are indexed by v, a piecewise-linear map of u: v = u below ua (one row per
-        // grid step), v = ua + (u - ua) / H above it (one row per H steps, H = 1, 2 or 4) -- on the lane
-        // v = min(u, fma(u, hinv, hc)), hc = ua (1 - hinv). A cell (rows k, k + 1) is "bad" when some band
-        // knot in it is off by more than max(kCgRelTol scale, kCgAbsTol peak) on the rows (the error of
-        // two piecewise-linear functions peaks at a knot of one or the other, and at the row positions R is
-        // the band's own lerp, rounded once); a bad cell's row carries a NaN in slot 0's first value and
-        // its lanes read the bands' own tables instead (cg_fix), so every served value is within the bound.
-        // The range [u1start, u1lim), ua and H are chosen to maximise the record weight served by good
-        // cells (records per unit u fall off as 1 / u past the near field: the octree's aggregated nodes
-        // grow with distance), a bad cell counting against it, within kCgMaxRows rows (+ one pad row).
-        double peak[4] = {0.0, 0.0, 0.0, 0.0};  // each band's largest |T|
-        for (int j = 0; j < 4; ++j)
-            if (pre) {  // (the GPU scan's, common_grid_gpu.hip: a maximum, the same bits in any order)
-                peak[j] = pre->peak[g][j];
-            } else if (groups.band[g][j] >= 0) {
-                const float *T = tab + (size_t)groups.band[g][j] * L;
-                for (int k = 0; k < L; ++k) peak[j] = std::max(peak[j], std::fabs((double)T[k]));
-            }
-        // the value a knot's error is relative to: the band's own |T[s]|; for the rgbprofile's R, G, B
-        // (rgb) the largest of the three at that distance -- FromRGB's outputs are sums of the three
-        // with weights of order one, so each component's error counts against their scale, not its own
-        // (B, ~15x shorter reach, falls orders of magnitude under R and G soon past the near field)
-        auto scale = [&](int j, int k) -> double {
-            const float *T = tab + (size_t)groups.band[g][j] * L;
-            double v = std::fabs((double)T[k]);
-            if (!rgb) return v;
-            const double u = (double)k / r[j];
-            for (int q = 0; q < 4; ++q) {
-                const int c = groups.band[g][q];
-                if (c < 0 || q == j) continue;
-                const double f = u * r[q];
-                if (f > (double)(L - 1)) continue;
-                const int sidx = std::min((int)std::floor(f), L - 2);
-                const double t = f - sidx;
-                const float *Tq = tab + (size_t)c * L;
-                v = std::max(v, std::fabs((1.0 - t) * (double)Tq[sidx] + t * (double)Tq[sidx + 1]));
-            }
-            return v;
-        };
-        // |rows - T| at band j's knot k on a grid of H steps (cells [H m, H (m + 1))), inf = bad
-        auto knot_err = [&](int j, int k, int H) -> double {
-            const float *T = tab + (size_t)groups.band[g][j] * L;
-            const double u = (double)k / r[j];
-            const int64_t m = (int64_t)std::floor(u / H);
-            const double t = (u - (double)(H * m)) / H;
-            const double approx = (1.0 - t) * R(j, H * m) + t * R(j, H * (m + 1));
-            const double err = std::fabs(approx - (double)T[k]);
-            return err > std::max(kCgRelTol * scale(j, k), kCgAbsTol * peak[j]) ? INFINITY : err;
-        };
-        static constexpr int kH[3] = {1, 2, 4};
-        const int ncell = L + 2;  // cells of the fine grid (u < L); coarse grids: ncell / H + 1
-        std::vector<uint8_t> bad[3];
-        for (int hi = 0; hi < 3; ++hi) bad[hi].assign((size_t)ncell / kH[hi] + 2, 0);
-        std::vector<double> fine_bad;  // u of the fine grid's bad knots (the candidate range starts)
-        if (pre) {
-            // the three maps as the GPU scan left them (the same per-knot test, common_grid_gpu.hip). Only
-            // floor(u) of a bad fine knot is used below, and that is its cell in bad[0]: the set cells in
-            // ascending order stand for the sorted list, whatever order the GPU's threads ran in
-            for (int hi = 0; hi < 3; ++hi)
-                if (pre->bad[g][hi].size() == bad[hi].size()) bad[hi] = pre->bad[g][hi];
-            for (size_t m = 0; m < bad[0].size(); ++m)
-                if (bad[0][m]) fine_bad.push_back((double)m);
-        }
-        for (int j = 0; j < 4 && !pre; ++j) {
-            if (groups.band[g][j] < 0) continue;
-            for (int k = std::max(0, (int)std::floor((double)u0f * r[j]) - 1); k < L - 1; ++k) {
-                const double u = (double)k / r[j];
-                for (int hi = 0; hi < 3; ++hi)
-                    if (knot_err(j, k, kH[hi]) == INFINITY) {
-                        bad[hi][(size_t)std::floor(u / kH[hi])] = 1;
-                        if (hi == 0) fine_bad.push_back(u);
-                    }
-            }
-        }
-        std::sort(fine_bad.begin(), fine_bad.end());
-        // a cell within a step of a band's profile end (u_end = (L - 1) / r_j) is flagged too: there the
-        // lanes take the own path, whose pairs carry sampleProfile's exact cutoff (multipole.cpp:65-66);
-        // past it the band's rows are exactly 0 (R is 0 from u_end + 1 on), before it every lane's f_j is
-        // at least one table step below L - 1 -- so the combine needs no range test
-        for (int j = 0; j < 4; ++j) {
-            if (groups.band[g][j] < 0) continue;
-            const double ue = (double)(L - 1) / r[j];
-            for (int hi = 0; hi < 3; ++hi) {
-                const int H = kH[hi];
-                const int64_t m0 = std::max<int64_t>(0, (int64_t)std::floor((ue - 1.0) / H));
-                const int64_t m1 = (int64_t)std::floor((ue + 2.0) / H);
-                for (int64_t m = m0; m <= m1 && m < (int64_t)bad[hi].size(); ++m) bad[hi][(size_t)m] = 1;
-            }
-        }
-        // prefix scores per grid: a good cell +w, a bad one -w, w = the cell's share of records (~ H / u)
-        std::vector<double> P[3], W0(bad[0].size() + 1, 0.0);  // (W0: the fine cells' weights, unsigned)
-        for (size_t m = 0; m < bad[0].size(); ++m) W0[m + 1] = W0[m] + 1.0 / std::max(1.0, (double)m + 0.5);
-        for (int hi = 0; hi < 3; ++hi) {
-            const int H = kH[hi];
-            const size_t n = bad[hi].size();
-            P[hi].assign(n + 1, 0.0);
-            for (size_t m = 0; m < n; ++m) {
-                const double w = (double)H / std::max(1.0, (double)H * ((double)m + 0.5));
-                P[hi][m + 1] = P[hi][m] + (bad[hi][m] ? -w : w);
-            }
-        }
-        // argmax of P over an index range (sparse table per grid)
-        std::vector<std::vector<uint32_t>> sp[3];
-        for (int hi = 0; hi < 3; ++hi) {
-            const size_t n = P[hi].size();
-            sp[hi].push_back(std::vector<uint32_t>(n));
-            for (size_t i = 0; i < n; ++i) sp[hi][0][i] = (uint32_t)i;
-            for (size_t lv = 1; ((size_t)1 << lv) <= n; ++lv) {
-                const std::vector<uint32_t> &a = sp[hi][lv - 1];
-                std::vector<uint32_t> b(n - ((size_t)1 << lv) + 1);
-                for (size_t i = 0; i < b.size(); ++i) {
-                    const uint32_t x = a[i], y = a[i + ((size_t)1 << (lv - 1))];
-                    b[i] = P[hi][y] > P[hi][x] ? y : x;
-                }
-                sp[hi].push_back(std::move(b));
-            }
-        }
-        auto argmax = [&](int hi, size_t lo, size_t hi_incl) -> size_t {  // first index of the max
-            size_t lv = 0;
-            while (((size_t)2 << lv) <= hi_incl - lo + 1) ++lv;
-            const uint32_t x = sp[hi][lv][lo], y = sp[hi][lv][hi_incl + 1 - ((size_t)1 << lv)];
-            return P[hi][y] > P[hi][x] ? y : x;
-        };
-        const int64_t cap = cg_max_rows();
-        const int64_t uend = (int64_t)L - 1;  // the rows serve u < u1lim <= L - 1
-        // candidate starts: the near field's end, and just past each of the first bad fine knots
-        std::vector<double> starts{(double)u0f};
-        for (const double b : fine_bad) {
-            if (starts.size() >= 64) break;
-            const double st = std::floor(b) + 2.0;
-            if (st > starts.back() && st < (double)uend) starts.push_back(st);
-        }
-        double best = 0.0, bstart = u0f;
-        int64_t bua = 0, bu1 = 0;
-        int bh = 0;
-        // (the rows always begin at the near field's end, so that a lane's row path is u0lim <= u < u1lim:
-        // one compare; the cells before the chosen start st are flagged)
-        const int64_t vbase = std::max<int64_t>(0, (int64_t)std::floor((double)u0f) - 1);
-        const int64_t c0 = (int64_t)std::floor((double)u0f);
-        for (const double st : starts) {
-            const int64_t sb = (int64_t)std::floor(st);
-            const double pre = W0[(size_t)sb] - W0[(size_t)c0];  // the flagged cells before st
-            // H = 1: fine rows only, [st, u1)
-            {
-                const int64_t hiu = std::min<int64_t>(uend, vbase + cap);
-                if (hiu > sb) {
-                    const size_t e = argmax(0, (size_t)sb + 1, (size_t)hiu);
-                    const double sc = P[0][e] - P[0][sb] - pre;
-                    if (sc > best) {
-                        best = sc, bstart = st, bua = (int64_t)e, bu1 = (int64_t)e, bh = 0;
-                    }
-                }
-            }
-            // H = 2, 4: fine rows [st, ua), coarse rows [ua, u1), ua a multiple of 64 (so hc is exact)
-            for (int hi = 1; hi < 3; ++hi) {
-                const int H = kH[hi];
-                for (int64_t ua = ((sb + 64) / 64) * 64; ua < uend; ua += 64) {
-                    const int64_t left = cap - (ua - vbase);
-                    if (left < 2) break;
-                    const double sf = P[0][ua] - P[0][sb];
-                    const int64_t m0 = ua / H;
-                    const int64_t mhi = std::min<int64_t>(m0 + left, uend / H);
-                    if (mhi <= m0) continue;
-                    const size_t e = argmax(hi, (size_t)m0 + 1, (size_t)mhi);
-                    const double sc = sf + P[hi][e] - P[hi][m0] - pre;
-                    if (sc > best) best = sc, bstart = st, bua = ua, bu1 = (int64_t)e * H, bh = hi;
-                }
-            }
-        }
-        const int H = kH[bh];
-        cg.hinv[g] = 1.f;
-        cg.hc[g] = 0.f;
-        cg.ua[g] = (float)L;
-        if (!(best > 0.0) || bu1 <= (int64_t)bstart + 1) {  // no accurate range: the exact tables past the near field
-            cg.u1lim[g] = cg.u1start[g] = u0f;
-            cg.ubase[g] = 0;
-            return;
-        }
-        const int64_t ua = bh ? bua : bu1;  // (H = 1: every row fine)
-        if (bh) {
-            cg.hinv[g] = 1.f / (float)H;
-            cg.hc[g] = (float)((double)ua * (1.0 - 1.0 / H));  // exact: ua a multiple of 64
-            cg.ua[g] = (float)ua;
-        }
-        const int64_t v1 = ua + (bu1 - ua) / H;  // v(u1); lanes read rows <= v1 (v may round up to v1)
-        auto upos = [&](int64_t v) -> int64_t { return v <= ua ? v : ua + (int64_t)H * (v - ua); };
-        const int64_t sfirst = (int64_t)std::floor(bstart);  // the first cell the chosen stretch serves
-        auto cell_bad = [&](int64_t v) -> bool {
-            const int64_t u = upos(v);
-            if (u < sfirst && u >= c0) return true;  // (the row below c0 is never read)
-            return v < ua ? bad[0][(size_t)u] != 0 : bad[bh][(size_t)(u / H)] != 0;
-        };
-        cg.ubase[g] = (uint32_t)vbase;
-        cg.u1start[g] = (float)bstart;  // (u0f, or an integer below 2^24)
-        cg.u1lim[g] = (float)bu1;
-        for (int64_t v = vbase; v <= v1; ++v) {
-            const int64_t u = upos(v), un = upos(v + 1);
-            float vv[4][2];
-            for (int j = 0; j < 4; ++j) {
-                vv[j][0] = R(j, u);
-                vv[j][1] = R(j, un);
-            }
-            if (cell_bad(v)) vv[0][0] = NAN;  // its lanes read the bands' own tables (cg_fix)
-            h.push_back(make_float4(vv[0][0], vv[0][1], vv[1][0], vv[1][1]));
-            h.push_back(make_float4(vv[2][0], vv[2][1], vv[3][0], vv[3][1]));
-        }
-        for (int j = 0; j < 4; ++j) {  // the error over the knots the good rows serve
-            const int c = groups.band[g][j];
-            if (c < 0) continue;
-            const float *T = tab + (size_t)c * L;
-            double l1 = 0.0, emax = 0.0, esum = 0.0;
-            for (int k = 0; k < L; ++k) l1 += std::fabs(T[k]);
-            for (int k = std::max(0, (int)std::floor(bstart * r[j]) - 1); k < L - 1; ++k) {
-                const double u = (double)k / r[j];
-                if (u < bstart) continue;
-                if (u >= (double)bu1) break;
-                const int Hk = u < (double)ua ? 1 : H;
-                const int64_t v = u < (double)ua ? (int64_t)std::floor(u) : ua + (int64_t)std::floor((u - ua) / H);
-                if (cell_bad(v)) continue;
-                const double e = knot_err(j, k, Hk);
-                // (relative error -- to scale(): the band's own value, or the largest of R, G, B -- where
-                // the relative bound governs: scale >= kCgAbsTol / kCgRelTol of the peak)
-                const double sc = scale(j, k);
-                if (kCgRelTol * sc >= kCgAbsTol * peak[j]) emax = std::max(emax, e / sc);
-                esum += e;
-            }
-            relg[g][j] = (float)emax;
-            l1g[g][j] = (float)(l1 > 0.0 ? esum / l1 : 0.0);
-        }
-        anyg[g] = true;
-    };
-    bool same = rgb;  // (rgb: every group's slots are the same three profiles)
-    for (int g = 1; g < kGroups && same; ++g)
-        for (int j = 0; j < 4; ++j) same = same && groups.band[g][j] == groups.band[0][j];
-    if (same) {
-        build_group(0);
-        for (int g = 1; g < kGroups; ++g) {
-            hg[g] = hg[0];
-            for (int j = 0; j < 4; ++j) {
-                cg.lrow[g][j] = cg.lrow[0][j];
-                cg.lcnt[g][j] = cg.lcnt[0][j];
-                cg.tau[g][j] = cg.tau[0][j];
-                relg[g][j] = relg[0][j];
-                l1g[g][j] = l1g[0][j];
-            }
-            cg.u0lim[g] = cg.u0lim[0];
-            cg.rg[g] = cg.rg[0];
-            cg.lds_r2[g] = cg.lds_r2[0];
-            cg.ubase[g] = cg.ubase[0];
-            cg.u1start[g] = cg.u1start[0];
-            cg.u1lim[g] = cg.u1lim[0];
-            cg.ua[g] = cg.ua[0];
-            cg.hinv[g] = cg.hinv[0];
-            cg.hc[g] = cg.hc[0];
-            anyg[g] = anyg[0];
-            failg[g] = failg[0];
-        }
-    } else {
-        std::vector<std::thread> th;
-        for (int g = 0; g < kGroups; ++g) th.emplace_back(build_group, g);
-        for (std::thread &t : th) t.join();
-    }
-    bool any = false;
-    for (int g = 0; g < kGroups; ++g) {
-        if (failg[g]) return false;
-        cg.row0[g] = (uint32_t)(h.size() / 2);
-        h.insert(h.end(), hg[g].begin(), hg[g].end());
-        any = any || anyg[g];
-        for (int j = 0; j < 4; ++j) {
-            const int c = groups.band[g][j];
-            if (c < 0) continue;
-            cg_rel_err[c] = std::max(cg_rel_err[c], relg[g][j]);
-            cg_l1_err[c] = std::max(cg_l1_err[c], l1g[g][j]);
-        }
-    }
-    cg.on = any ? 1 : 0;
-    return any;
-}
-
-void DeviceProfile::set_rgb(const float *tab) {
-    static const float refl[7][NB] = {MPSS_BAND_RGBREFL2SPECTWHITE_INIT, MPSS_BAND_RGBREFL2SPECTCYAN_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTMAGENTA_INIT, MPSS_BAND_RGBREFL2SPECTYELLOW_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTRED_INIT, MPSS_BAND_RGBREFL2SPECTGREEN_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTBLUE_INIT};
-    rgb_refl.upload(&refl[0][0], 7 * NB);
-    // the common grid of the R, G, B profiles (rows 0..2, the same three slots in every group: the
-    // sharded gather reads them in band_tree's lband order)
-    BandGroups g3 = groups;
-    for (int g = 0; g < kGroups; ++g)
-        for (int j = 0; j < 4; ++j) g3.band[g][j] = j < 3 ? j : -1;
-    build_common(tab, g3, 28, true);  // (the LDS's last 28 floats: the groups' FromRGB weights)
-}
-
-void DeviceProfile::build_common(const float *tab, const BandGroups &slots, int lds_reserve, bool rgb) {
-    ctab.release();
-    ctab_half.release();
-    // the two LDS layouts' grids side by side (host work: each builds its groups on threads of its own)
-    std::vector<float4> hh, h;
-    bool ok_half = false;
-    // the GPU builder: the per-knot scan of both layouts and all groups in one go, from the table
-    // already on the device (the rgbprofile's rows 0..2 are the first rows of the same table)
-    std::unique_ptr<CgScan[]> scan;
-    if (!grid_on_host) {
-        scan.reset(new CgScan[2]);
-        if (!scan_common_grid_gpu(table.ptr, L, host_rcp, slots, lds_reserve, rgb, scan.get())) scan.reset();
-    }
-    std::thread half([&] {
-        ok_half = build_common_grid(tab, L, host_rcp, slots, cg_half, hh, cg_rel_err[1], cg_l1_err[1], 5088,
-                                    lds_reserve, rgb, scan ? &scan[1] : nullptr);
-    });
-    const bool ok = build_common_grid(tab, L, host_rcp, slots, cg, h, cg_rel_err[0], cg_l1_err[0], 10236,
-                                      lds_reserve, rgb, scan ? &scan[0] : nullptr);
-    half.join();
-    if (ok_half) {
-        ctab_half.upload(hh.data(), hh.size());
-        cg_half.tab = ctab_half.ptr;
-    } else {
-        cg_half.on = 0;
-    }
-    if (!ok) {
-        cg.on = 0;  // the per-band tables stay in use
-        return;
-    }
-    ctab.upload(h.data(), h.size());
-    cg.tab = ctab.ptr;
 }
 
 namespace {

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/mpss.h"
+#include "common_grid.h"
 #include "context.h"
 #include "material.h"
 #include "mc_profile.h"

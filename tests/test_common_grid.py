@@ -1,5 +1,5 @@
-"""The common grid of the sharded Mo() gather (mpss_config.mo_common_grid; mo_band.h CommonGrid),
-host half, on the CPU: the LDS split, the resampled pair rows and the range they serve, against a
+"""The common grid of the sharded Mo() gather (mpss_config.mo_common_grid; common_grid_types.h CommonGrid),
+the host builder (csrc/common_grid.cpp), on the CPU: the LDS split, the resampled pair rows and the range they serve, against a
 numpy restatement of multipole.cpp:60-73's sampleProfile (every served knot within 2e-6 of the
 band's own value, or 1e-14 of the band's peak in the far tails).
 
@@ -13,11 +13,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden.npz")
 NEAR_FIELDS = (5088, 10236)  # mpss_config.mo_near_field: the default layout and the one-workgroup one
-ABS_TOL = 1e-14  # mo_kernel.h kCgAbsTol
+ABS_TOL = 1e-14  # common_grid_math.h kCgAbsTol
 
 
 def _groups(rcp):
-    """make_band_groups (mo_band.h): bands by increasing rcp, runs of 4, 4, 4, 4, 4, 4, 3, 3."""
+    """make_band_groups (common_grid_types.h): bands by increasing rcp, runs of 4, 4, 4, 4, 4, 4, 3, 3."""
     order = np.argsort(rcp, kind="stable")
     return [list(order[i * 4:(i + 1) * 4]) for i in range(6)] + [list(order[24:27]), list(order[27:30])]
 

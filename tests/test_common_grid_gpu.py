@@ -3,7 +3,8 @@ knot on the device) must build the host builder's grid bit for bit: Context.comm
 the context built, against mpss.host_common_grid of the same table, field for field and with the rows as
 uint32 bit patterns (the NaN flag's pattern included), for both LDS layouts.
 
-Cases: the smallest tables that reach each branch of build_common_grid, installed with
+Cases: the smallest tables that reach each branch of build_common_grid (csrc/common_grid.cpp; both
+builders compute through csrc/common_grid_math.h), installed with
 set_material_tables, and LayeredSkin materials built by add_layeredskin. One more case renders a tissue
 window with the GPU-built and with the host-built grid: the same film bytes.
 """
