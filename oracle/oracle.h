@@ -170,6 +170,13 @@ void o_envmap_lookup(const o_envmap *m, float s, float t, float out[3]);
 void o_envmap_sample(const o_envmap *m, float u0, float u1, float uv[2], float *pdf);
 float o_envmap_pdf(const o_envmap *m, float u, float v);
 long o_tessellate(const o_scene *s, float min_dist, int incenter, o_surface_point *out, long cap);
+/* The scene's own ray tracer (Scene::Intersect / IntersectP: triangles and sphere lights) for n rays
+ * o, d with per-ray [mint, maxt]; the BVH is built on first use. tri: global triangle id (meshes in
+ * the order added), -1 - l for sphere light l, INT_MIN for a miss (t = maxt, b1 = b2 = 0). */
+void o_trace_closest(o_scene *s, int n, const float *o, const float *d, const float *mint, const float *maxt,
+                     float *t, int32_t *tri, float *b1, float *b2);
+void o_trace_any(o_scene *s, int n, const float *o, const float *d, const float *mint, const float *maxt,
+                 uint8_t *hit);
 
 /* ---- the reference sampler (samplerrenderer.cpp:60-225, lowdiscrepancy.cpp:40-93,
  *      montecarlo.{h:254-333, cpp:200-250}, multipolesubsurface.cpp:72-152) ----

@@ -1083,6 +1083,27 @@ static int occluded(const o_scene *s, v3 o, v3 d, float mint, float maxt) {
     return 0;
 }
 
+/* The tracer itself, exported so a test can pin it (tests/test_trace_oracle.py): n rays o, d (3 floats
+ * each) with their own [mint, maxt]. tri: the global triangle id (meshes in the order they were
+ * added), -1 - l for sphere light l, INT_MIN for a miss (then t = maxt and b1 = b2 = 0). */
+void o_trace_closest(o_scene *s, int n, const float *o, const float *d, const float *mint, const float *maxt,
+                     float *t, int32_t *tri, float *b1, float *b2) {
+    scene_prepare(s);
+    for (int i = 0; i < n; ++i) {
+        hit_t h = intersect(s, ld(o, i), ld(d, i), mint[i], maxt[i]);
+        t[i] = h.t;
+        tri[i] = h.tri;
+        b1[i] = h.tri >= 0 ? h.b1 : 0.f;
+        b2[i] = h.tri >= 0 ? h.b2 : 0.f;
+    }
+}
+
+void o_trace_any(o_scene *s, int n, const float *o, const float *d, const float *mint, const float *maxt,
+                 uint8_t *hit) {
+    scene_prepare(s);
+    for (int i = 0; i < n; ++i) hit[i] = (uint8_t)occluded(s, ld(o, i), ld(d, i), mint[i], maxt[i]);
+}
+
 /* ------------------------------------------------------------------ tessellation */
 typedef struct { float b0, b1, b2; } bary;
 static const bary CENTROID = {1.f / 3.f, 1.f / 3.f, 1.f / 3.f};

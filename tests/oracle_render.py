@@ -15,6 +15,7 @@ NB = 30
 f32p = oracle_lib.f32p
 vp = C.c_void_p
 
+NO_HIT = -2 ** 31  # o_trace_closest's tri for a miss
 SURFACE_POINT = np.dtype([("p", "<f4", 3), ("n", "<f4", 3), ("u", "<f4"), ("v", "<f4"), ("material", "<u4"),
                           ("area", "<f4"), ("ray_eps", "<f4")])
 
@@ -68,6 +69,10 @@ def _lib():
     L.o_render_task_count.restype = C.c_int
     L.o_render_task_count.argtypes = [C.c_int, C.c_int, C.c_int]
     L.o_sub_window.argtypes = [C.c_int] * 6 + [vp]
+    L.o_trace_closest.restype = None
+    L.o_trace_closest.argtypes = [vp, C.c_int, f32p, f32p, f32p, f32p, f32p, oracle_lib.i32p, f32p, f32p]
+    L.o_trace_any.restype = None
+    L.o_trace_any.argtypes = [vp, C.c_int, f32p, f32p, f32p, f32p, vp]
     L._render_sigs = True
     return L
 
@@ -231,6 +236,30 @@ class OracleScene:
 
     def __del__(self):
         self.close()
+
+    @staticmethod
+    def _rays(o, d, mint, maxt):
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        o = np.ascontiguousarray(np.broadcast_to(np.asarray(o, np.float32), d.shape))
+        lo = np.ascontiguousarray(np.broadcast_to(np.float32(mint), len(d)))
+        hi = np.ascontiguousarray(np.broadcast_to(np.float32(maxt), len(d)))
+        return o, d, lo, hi
+
+    def trace_closest(self, o, d, mint=0.0, maxt=np.inf):
+        """The oracle's Scene::Intersect for rays o (3,) or (n, 3), d (n, 3): t, tri, b1, b2 with tri the
+        global triangle id (meshes in scene order), -1 - l for sphere light l, NO_HIT for a miss."""
+        o, d, lo, hi = self._rays(o, d, mint, maxt)
+        t, b1, b2 = (np.zeros(len(d), np.float32) for _ in range(3))
+        tri = np.zeros(len(d), np.int32)
+        _lib().o_trace_closest(self.h, len(d), o, d, lo, hi, t, tri, b1, b2)
+        return t, tri, b1, b2
+
+    def trace_any(self, o, d, mint, maxt):
+        """The oracle's Scene::IntersectP for the same rays: a bool per ray."""
+        o, d, lo, hi = self._rays(o, d, mint, maxt)
+        hit = np.zeros(len(d), np.uint8)
+        _lib().o_trace_any(self.h, len(d), o, d, lo, hi, hit.ctypes.data)
+        return hit.astype(bool)
 
     def tessellate(self, incenter=False):
         L = _lib()

@@ -102,7 +102,7 @@ def test_c1_tissue_full_frame(mpss, oracle):
     assert (sc.xres, sc.yres, sc.spp) == (256, 256, 8)
     ctx = pbrtscene.build_context(sc)
     ctx.preprocess(seed=2)
-    o = orr.OracleScene(sc, orr.tables_from_ctx(ctx, len(sc.materials)), ctx.cfg, mpss)
+    o = orr.OracleScene(sc, orr.tables_from_oracle(sc), ctx.cfg, mpss)
     pts = ctx.surface_points()
     assert pts.tobytes() == o.tessellate().tobytes()
     E = o.irradiance(pts, 2)

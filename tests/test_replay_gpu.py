@@ -23,6 +23,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _scene(name, lights=None, W=40, H=32, spp=4):
     from mpss import pbrtscene
+    if name == "shard_cloud":  # tests/synth.py: the camera inside a cloud of shards, 7 sign octants in frame
+        import copy
+        import synth
+        sc = copy.copy(synth.shard_cloud())
+        sc.materials = [dict(sc.materials[0], desired_length=64)]
+        return sc
     sc = pbrtscene.load(os.path.join(ROOT, "scenes", name), xres=W, yres=H, spp=spp)
     sc.integrator["minsampledistance"] = 0.008
     for m in sc.materials:
@@ -100,7 +106,7 @@ def _render(torch, ctx, sc, rects):
 @pytest.mark.parametrize("name,lights,cores", [("skin.pbrt", None, 8), ("skin.pbrt", "sky+area", 8),
                                                ("tissue.pbrt", None, 2), ("skin.pbrt", "24 spheres", 8),
                                                ("skin.pbrt", "ns=5", 8), ("skin.pbrt", "ns=16", 8),
-                                               ("skin.pbrt", "edge geometry", 8)])
+                                               ("skin.pbrt", "edge geometry", 8), ("shard_cloud", None, 8)])
 def test_replay_table_bit_exact(mpss, oracle, name, lights, cores):
     sc = _scene(name, lights, W=128, H=96) if lights == "edge geometry" else _scene(name, lights)
     torch, ctx, o = _pair(mpss, sc, cores)
