@@ -390,6 +390,46 @@ int mpss_mc_profile(mpss_ctx *ctx, const mpss_layer *layers, int nlayers, float 
 int mpss_mc_reference(const mpss_layer *layers, int nlayers, float mfp_range, int nsegments, int lerp_on_thin_slab,
                       double *reflectance, double *transmittance, double *total_r, double *total_t);
 
+/* ---- sum-of-Gaussians profile fit (renderer "multipoleprofilefit", src/renderers/profilefit.cpp:158-379,
+ * src/multipole/MultipoleProfileCalculator/gaussianfit.cpp:42-154) ---- */
+typedef struct {
+    const float *f_mel, *f_eu, *f_blood, *f_ohg;   /* the four ranges; sorted ascending here, as FindParamRange */
+    uint32_t n_f_mel, n_f_eu, n_f_blood, n_f_ohg;  /* ids: f_mel outermost, f_ohg innermost (ForRanges) */
+    float layer_thickness_nm[2];  /* "skinlayer layers" thickness (nm); the fit works in mm (thickness / 1e6) */
+    float layer_ior[2];           /* "skinlayer layers" ior */
+    int desired_length;           /* "desiredProfileLength" = 256 */
+    int id_min, id_max;           /* "idrange" = 0, -1: ids [max(0, id_min), id_max < 0 ? all : min(all, id_max)) */
+    int max_profiles_per_batch;   /* profiles (id x band) per pass through the transform grids; 0: as many as
+                                     8 GB of grids hold. Results do not depend on it */
+} mpss_profilefit;
+void mpss_profilefit_defaults(mpss_profilefit *f);
+/* DoProfileFit on the ctx's GPU: one FP64 multipole profile per (id, band) (GaussianFitTask::Run), every
+ * candidate window of 6 consecutive sigmas fitted (GF_FitSumGaussians), the window of least overallError
+ * kept. Sizes first: *n_sigmas and *n_ids are always written, and sigmas[*n_sigmas] when it is not NULL;
+ * with coeffs NULL nothing else runs. Outputs: coeffs [n_ids][30][n_sigmas] (normalised coefficients, zero
+ * outside the chosen window), error [n_ids][30] (overallError), rgb_coeffs [n_ids][3][n_sigmas]
+ * (ToRGBSpectrum of each sigma's 30 coefficients), centre [n_ids][30] (chosen centre index: the window is
+ * sigmas[centre - 3 .. centre + 2]); each of error / rgb_coeffs / centre may be NULL. The profiles go through
+ * the stages batch by batch, and each batch is fitted before the next one's profiles overwrite its d^2 and R:
+ * device memory is bounded by the batch, not by the grid. Everything is allocated and uploaded before the
+ * first batch is queued; from then to the final copy back the host only queues work on `stream` -- no wait
+ * and no copy between a batch's profile stage and its fit. stage_ms (nullable, 3 doubles): HIP-event times
+ * of the profile stages and of the fit stages, summed over the batches, and the number of batches run.
+ * A band no candidate window passes for (the reference would read a null pointer) is
+ * MPSS_ERR_INTERNAL naming the id and band. An empty id range gives *n_ids = 0. Needs no scene.
+ * Synchronous on stream; serialised like the calls that change the context. */
+int mpss_profile_fit(mpss_ctx *ctx, const mpss_profilefit *f, uint32_t *n_sigmas, uint32_t *n_ids, float *sigmas,
+                     float *coeffs, float *error, float *rgb_coeffs, int32_t *centre, double *stage_ms, void *stream);
+/* The fit stage alone on caller-supplied host arrays: dist_sq / data [n_profiles][length] (a profile's d^2
+ * and R; the fit takes r = sqrtf(d^2)), sigmas [n_sigmas] ascending, mfp_min / mfp_max [n_profiles] (the
+ * candidate filter: centres 3 .. n_sigmas - 3 with mfp_min / 2 <= sigma <= mfp_max * 2). Outputs: coeffs
+ * [n_profiles][n_sigmas], error [n_profiles], centre [n_profiles]; nullable cand_error [n_profiles][n_sigmas]
+ * (NaN where the centre is no candidate) and cand_coeffs [n_profiles][n_sigmas][6]. A profile without a
+ * candidate: MPSS_ERR_INTERNAL naming it (the outputs are written, its centre -1). */
+int mpss_sog_fit(mpss_ctx *ctx, uint32_t n_profiles, uint32_t length, const float *dist_sq, const float *data,
+                 uint32_t n_sigmas, const float *sigmas, const float *mfp_min, const float *mfp_max, float *coeffs,
+                 float *error, int32_t *centre, float *cand_error, float *cand_coeffs, void *stream);
+
 /* ---- host-side utilities (no HIP device needed): the product's own parse-time builders,
  * exposed so their results can be checked on a CPU-only machine. ---- */
 /* SampledSpectrum::FromRGB (spectrum.cpp:103-187); pbrt's "color"/"rgb" parameters use
@@ -445,6 +485,29 @@ int mpss_host_common_grid(const float *table, uint32_t L, const float *rcp, int 
 int mpss_get_common_grid(mpss_ctx *ctx, uint32_t material_id, int near_field, float *rows, uint32_t *n_rows,
                          int32_t *bands, float *rg, float *u0lim, float *u1lim, float *u1start, uint32_t *row0,
                          uint32_t *ubase, float *rel_err, float *l1_err, float *ua, float *hinv, int *ok);
+/* mpss_sog_fit's arguments without a context: the fit restated on the host in FP64, every sum in the
+ * reference's sequential order (the in-library check of the kernel, and the path for a machine without a
+ * device). cand_gram (nullable): [n_profiles][n_sigmas][36], each candidate's Gram matrix X, row-major
+ * (entries of centres that are no candidate are left untouched). */
+int mpss_host_sog_fit(uint32_t n_profiles, uint32_t length, const float *dist_sq, const float *data,
+                      uint32_t n_sigmas, const float *sigmas, const float *mfp_min, const float *mfp_max,
+                      float *coeffs, float *error, int32_t *centre, float *cand_error, float *cand_coeffs,
+                      double *cand_gram);
+/* LinearSolve (gaussianfit.cpp:48-96) for 6 unknowns, a row-major. quirk 1: as the reference, the pivot row
+ * searched in the original matrix; 0: in the partly eliminated one (what the fit does NOT use). */
+int mpss_host_sog_solve(const double *a, const double *b, int quirk, double *x);
+/* mpss_profile_fit on the host: host profiles (the FFTs of mpss_host_build_profile) and mpss_host_sog_fit.
+ * profiles_dist_sq / profiles_data (nullable): [n_ids][30][*length] resampled profiles as the fit read them;
+ * *length (nullable) is always written. */
+int mpss_host_profile_fit(const mpss_profilefit *f, uint32_t *n_sigmas, uint32_t *n_ids, float *sigmas,
+                          float *coeffs, float *error, float *rgb_coeffs, int32_t *centre, uint32_t *length,
+                          float *profiles_dist_sq, float *profiles_data);
+/* The parameters of id (ParamsFromId): out[4] = f_mel, f_eu, f_blood, f_ohg. */
+int mpss_profilefit_params(const mpss_profilefit *f, uint32_t id, float *out);
+/* The layers of id as the fit builds them, in millimetres (CreateGaussianFitTasks, profilefit.cpp:262-274):
+ * mua / musp [2][30] (the 1 / cm band values over 10), thickness [2] (nm over 1e6), eta [2]. */
+int mpss_profilefit_layers(const mpss_profilefit *f, uint32_t id, float *mua, float *musp, float *thickness,
+                           float *eta);
 /* Octree build + pre-order export (sizes first with NULL outputs). */
 int mpss_host_octree_export(uint32_t n, const float *p, const float *nrm, const float *E, const float *area,
                             uint32_t *n_nodes, float *node_p, float *node_area, float *node_et, int32_t *depth,

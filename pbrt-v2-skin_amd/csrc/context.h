@@ -167,6 +167,12 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         return irradiance_;
     }
+    // for calls that use the context's device but none of its state (mpss_profile_fit, mpss_sog_fit):
+    // makes the device current and serialises the call against the context's other calls
+    std::unique_lock<std::mutex> lock_device() const {
+        activate();
+        return std::unique_lock<std::mutex>(mu_);
+    }
     bool has_octree() const { return have_octree_; }
     mpss_render_stats render_stats();
     void reset_render_stats();

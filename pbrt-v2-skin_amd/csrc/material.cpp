@@ -59,7 +59,11 @@ void wld_to_bands(const float w[WLD_N], float out[NB]) {
 }
 }  // namespace
 
-void skin_layer_params(const SkinParams &p, LayerParams &out) {
+namespace {
+// SkinCoefficients' four wavelength-dependent coefficients (skincoeffs.h:46-135) on the 61-entry WLD grid,
+// in the reference's own unit (1 / cm)
+void skin_wld_coeffs(float f_mel, float f_eu, float f_blood, float f_ohg, float ea[WLD_N], float es[WLD_N],
+                     float da[WLD_N], float ds[WLD_N]) {
     float base[WLD_N], eu[WLD_N], pheo[WLD_N], sct[WLD_N];
     for (int i = 0; i < WLD_N; ++i) {
         const float wl = wld_lambda(i);
@@ -71,16 +75,27 @@ void skin_layer_params(const SkinParams &p, LayerParams &out) {
     float oxy[WLD_N], deo[WLD_N];
     wld_resample(kOxy, oxy);
     wld_resample(kDeoxy, deo);
-    const float unit = p.nmperunit / 1e7f;  // layeredskin.cpp:47
     const float kblood = 2.303f / 64500.f * 150.f;
-    float ea[WLD_N], es[WLD_N], da[WLD_N], ds[WLD_N];
     for (int i = 0; i < WLD_N; ++i) {
-        const float mel = eu[i] * p.f_eu + pheo[i] * (1 - p.f_eu);
-        ea[i] = (mel * p.f_mel + base[i] * (1 - p.f_mel)) * unit;                    // mua_epi
-        es[i] = sct[i] * unit;                                                        // musp_epi
-        const float blood = (oxy[i] * p.f_ohg + deo[i] * (1.f - p.f_ohg)) * kblood;  // mua_blood
-        da[i] = (blood * p.f_blood + base[i] * (1 - p.f_blood)) * unit;               // mua_derm
-        ds[i] = (sct[i] * 0.5f) * unit;                                               // musp_derm
+        const float mel = eu[i] * f_eu + pheo[i] * (1 - f_eu);
+        ea[i] = mel * f_mel + base[i] * (1 - f_mel);                             // mua_epi
+        es[i] = sct[i];                                                          // musp_epi
+        const float blood = (oxy[i] * f_ohg + deo[i] * (1.f - f_ohg)) * kblood;  // mua_blood
+        da[i] = blood * f_blood + base[i] * (1 - f_blood);                       // mua_derm
+        ds[i] = sct[i] * 0.5f;                                                   // musp_derm
+    }
+}
+}  // namespace
+
+void skin_layer_params(const SkinParams &p, LayerParams &out) {
+    const float unit = p.nmperunit / 1e7f;  // layeredskin.cpp:47
+    float ea[WLD_N], es[WLD_N], da[WLD_N], ds[WLD_N];
+    skin_wld_coeffs(p.f_mel, p.f_eu, p.f_blood, p.f_ohg, ea, es, da, ds);
+    for (int i = 0; i < WLD_N; ++i) {
+        ea[i] *= unit;
+        es[i] *= unit;
+        da[i] *= unit;
+        ds[i] *= unit;
     }
     wld_to_bands(ea, out.mua[0]);
     wld_to_bands(es, out.musp[0]);
@@ -90,6 +105,39 @@ void skin_layer_params(const SkinParams &p, LayerParams &out) {
         out.thickness[l] = p.thickness_nm[l] / p.nmperunit;
         out.eta[l] = p.ior[l];
     }
+}
+
+// MultipoleProfileFitRenderer::CreateGaussianFitTasks (profilefit.cpp:262-274): millimetres -- the band
+// values of the 1 / cm coefficients over 10, thickness (nm) over 1e6
+void skin_fit_layer_params(float f_mel, float f_eu, float f_blood, float f_ohg, const float thickness_nm[2],
+                           const float ior[2], LayerParams &out) {
+    float w[4][WLD_N];
+    skin_wld_coeffs(f_mel, f_eu, f_blood, f_ohg, w[0], w[1], w[2], w[3]);
+    wld_to_bands(w[0], out.mua[0]);
+    wld_to_bands(w[1], out.musp[0]);
+    wld_to_bands(w[2], out.mua[1]);
+    wld_to_bands(w[3], out.musp[1]);
+    for (int l = 0; l < 2; ++l) {
+        for (int c = 0; c < NB; ++c) {
+            out.mua[l][c] = out.mua[l][c] / 10.f;
+            out.musp[l][c] = out.musp[l][c] / 10.f;
+        }
+        out.thickness[l] = thickness_nm[l] / 1e6f;
+        out.eta[l] = ior[l];
+    }
+}
+
+// DoProfileFit's mfp range (profilefit.cpp:287-300): 10 / (mua + musp) of both layers over the 61 entries
+// of the wavelength-dependent values (WLDValue::Min / Max run over those, not the 30 bands)
+void skin_fit_mfp_range(float f_mel, float f_eu, float f_blood, float f_ohg, float &mfp_min, float &mfp_max) {
+    float w[4][WLD_N];
+    skin_wld_coeffs(f_mel, f_eu, f_blood, f_ohg, w[0], w[1], w[2], w[3]);
+    for (int i = 0; i < WLD_N; ++i)
+        for (int l = 0; l < 2; ++l) {
+            const float mfp = 10.f / (w[2 * l][i] + w[2 * l + 1][i]);
+            mfp_min = std::min(mfp_min, mfp);
+            mfp_max = std::max(mfp_max, mfp);
+        }
 }
 
 // ------------------------------------------------------------ multipole profile
@@ -298,8 +346,9 @@ unsigned round_up_pow2(unsigned v) {
 }
 
 // One spectral channel (MultipoleProfileTask::Run, multipole.cpp:241-295)
-void channel_profile(const LayerParams &lp, int sc, int desired, bool lerp_thin, std::vector<float> &table,
-                     float &rcp, float &spacing, float &total) {
+// up to the unique-d^2 samples d, r (MPC_Output before resampling)
+void channel_samples(const LayerParams &lp, int sc, int desired, bool lerp_thin, std::vector<float> &d,
+                     std::vector<float> &r, float &total) {
     float mfp_total = 0.f;
     for (int l = 0; l < 2; ++l) mfp_total += 1.f / (lp.mua[l][sc] + lp.musp[l][sc]);
     const float mfp = mfp_total / (float)2;
@@ -344,12 +393,19 @@ void channel_profile(const LayerParams &lp, int sc, int desired, bool lerp_thin,
             ents.emplace_back(nsq, (float)R0[(size_t)(c + i) * N + (c + j)] * denorm);
         }
     std::sort(ents.begin(), ents.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
-    std::vector<float> d(ents.size()), r(ents.size());
+    d.resize(ents.size());
+    r.resize(ents.size());
     for (size_t k = 0; k < ents.size(); ++k) {
         d[k] = (float)ents[k].first * step * step;
         r[k] = ents[k].second;
     }
     total = (float)kahan(R0);
+}
+
+void channel_profile(const LayerParams &lp, int sc, int desired, bool lerp_thin, std::vector<float> &table,
+                     float &rcp, float &spacing, float &total) {
+    std::vector<float> d, r;
+    channel_samples(lp, sc, desired, lerp_thin, d, r, total);
     // MPC_ResampleForUniformDistanceSquaredDistribution (:404-426), target = 2 * length
     const unsigned tl = (unsigned)d.size() * 2;
     const float extent = d.back();
@@ -549,6 +605,24 @@ void build_profile(const LayerParams &lp, int desired_length, bool lerp_thin, Pr
         if ((int)tabs[c].size() != out.length) throw Error(-2, "profile channel lengths differ");
     out.table.resize((size_t)NB * out.length);
     for (int c = 0; c < NB; ++c) memcpy(&out.table[(size_t)c * out.length], tabs[c].data(), sizeof(float) * out.length);
+}
+
+// GaussianFitTask::Run's profile of one channel (profilefit.cpp:158-192): lerpOnThinSlab, resampled to the
+// sample count itself (MPC_ResampleForUniformDistanceSquaredDistribution(pOutput, pOutput->length))
+void fit_channel_profile(const LayerParams &lp, int sc, int desired_length, std::vector<float> &dsq,
+                         std::vector<float> &refl) {
+    std::vector<float> d, r;
+    float total;
+    channel_samples(lp, sc, desired_length, true, d, r, total);
+    const unsigned tl = (unsigned)d.size();
+    const float extent = d.back();
+    dsq.resize(tl);
+    refl.resize(tl);
+    for (unsigned i = 0; i < tl; ++i) {
+        const float q = (float)i * extent / (float)(tl - 1);
+        dsq[i] = q;
+        refl[i] = resample_at(d, r, q);
+    }
 }
 
 // ------------------------------------------------------------ rho_hd table

@@ -39,6 +39,33 @@ struct RhoTable {
 };
 
 void skin_layer_params(const SkinParams &p, LayerParams &out);
+// Renderer "multipoleprofilefit" (renderers/profilefit.cpp): a combination's layers in millimetres
+// (CreateGaussianFitTasks :262-274), the mfp range the sigma list is made from (DoProfileFit :287-300,
+// folded into mfp_min / mfp_max), and one channel's profile as the fit reads it (GaussianFitTask::Run
+// :158-192: d^2 and R resampled to the sample count itself)
+void skin_fit_layer_params(float f_mel, float f_eu, float f_blood, float f_ohg, const float thickness_nm[2],
+                           const float ior[2], LayerParams &out);
+void skin_fit_mfp_range(float f_mel, float f_eu, float f_blood, float f_ohg, float &mfp_min, float &mfp_max);
+void fit_channel_profile(const LayerParams &lp, int sc, int desired_length, std::vector<float> &dsq,
+                         std::vector<float> &refl);
+// The same profiles for n channels on the current HIP device (profile_gpu.hip). lp[i / NB] band i % NB is
+// channel i. Channels go through the transform grids in batches of at most max_batch (0: as many as 8 GB of
+// grids hold); a channel's result does not depend on the split. fit_profiles_prepare does every allocation
+// and (blocking) host copy for all n channels and returns the batch size; fit_profiles_launch queues one
+// batch (channels c0 .. c0 + nch - 1, nch <= the batch size) on `stream` -- a memset and kernels only -- and
+// writes its d^2 and R to dsq_dev / refl_dev [nch][fit_profile_samples(desired_length)].
+struct FitProfileWork {  // the builder's device workspace: keep it alive until the stream has run the work
+    DevBuf<double2> grids, tw;
+    DevBuf<unsigned char> setup;
+    DevBuf<int2> ij;
+    DevBuf<uint32_t> nsq;
+    DevBuf<float> step, d, r;
+    int n = 0, batch = 0, M = 0, logM = 0, ext = 0, nent = 0, cols = 0;
+    int batches = 0;  // launches so far
+};
+int fit_profile_samples(int desired_length);
+int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, FitProfileWork &work);
+void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitProfileWork &work, hipStream_t stream);
 // distinct: channels 0..distinct-1 are built and channel c >= distinct copies channel c % distinct
 // (rgbprofile: lp's band c already holds component c % 3, so 3 builds give all 30 rows)
 void build_profile(const LayerParams &lp, int desired_length, bool lerp_on_thin_slab, ProfileTables &out,

@@ -134,20 +134,23 @@ __device__ void lds_fft(double2 *a, int n, int logn, const double2 *__restrict__
 
 __device__ __forceinline__ int bitrev(int x, int logn) { return (int)(__builtin_bitreverse32((unsigned)x) >> (32 - logn)); }
 
-__global__ __launch_bounds__(256) void fft_rows_kernel(double2 *data, int M, int logM, const double2 *tw, int inverse) {
+// one row per workgroup; blockIdx.y picks a block of rows mat_stride elements apart (the folded inverse
+// transform of every channel's slot-0 grid)
+__global__ __launch_bounds__(256) void fft_rows_kernel(double2 *data, int M, int logM, const double2 *tw, int inverse,
+                                                       size_t mat_stride) {
     extern __shared__ double2 a_row[];
-    double2 *row = data + (size_t)blockIdx.x * M;
+    double2 *row = data + (size_t)blockIdx.y * mat_stride + (size_t)blockIdx.x * M;
     for (int k = threadIdx.x; k < M; k += blockDim.x) a_row[bitrev(k, logM)] = row[k];
     __syncthreads();
     lds_fft(a_row, M, logM, tw, inverse != 0);
     for (int k = threadIdx.x; k < M; k += blockDim.x) row[k] = a_row[k];
 }
 
-// 'cols' adjacent columns per workgroup; grid = (M / cols) x nmat
+// 'cols' adjacent columns per workgroup; grid = (M / cols) x nmat, matrices mat_stride elements apart
 __global__ __launch_bounds__(256) void fft_cols_kernel(double2 *data, int M, int logM, int cols, const double2 *tw,
-                                                       int inverse) {
+                                                       int inverse, size_t mat_stride) {
     extern __shared__ double2 a_col[];
-    double2 *mat = data + (size_t)blockIdx.y * M * M;
+    double2 *mat = data + (size_t)blockIdx.y * mat_stride;
     const int c0 = blockIdx.x * cols;
     for (int e = threadIdx.x; e < M * cols; e += blockDim.x) {
         const int r = e / cols, cc = e % cols;
@@ -286,6 +289,43 @@ const UniqueList &unique_list(unsigned ext) {
     return u;
 }
 
+// per-channel setup (channel_profile / layer_grid, material.cpp); returns the channel's step
+float chan_setup(const LayerParams &lp, int sc, int desired_length, bool lerp_thin, ChanSetup &c) {
+    float mfp_total = 0.f;
+    for (int l = 0; l < 2; ++l) mfp_total += 1.f / (lp.mua[l][sc] + lp.musp[l][sc]);
+    const float mfp = mfp_total / (float)2;
+    const float step = 12.f * mfp / (float)desired_length;
+    c.s2 = step * step;
+    c.nf = c.s2;
+    const float up[2] = {lp.eta[0], lp.eta[1] / lp.eta[0]}, lo[2] = {lp.eta[0] / lp.eta[1], lp.eta[1]};
+    for (int l = 0; l < 2; ++l) {
+        float thick = lp.thickness[l];
+        const float mua = lp.mua[l][sc], musp = lp.musp[l][sc];
+        const double mfp2 = 2. / (mua + musp);
+        double lerp = 1.;
+        if (lerp_thin) {
+            lerp = (thick < mfp2) ? (1. - exp(-thick * 2. / mfp2)) / (1. - exp(-2.)) : 1.;
+            if (thick < 0.01 * mfp2) thick = (float)(0.01 * mfp2);
+        }
+        c.lerp[l] = lerp;
+        for (int k = 0; k < kPairs; ++k) c.dip[l][k] = make_dipole(up[l], lo[l], thick, mua, musp, k - 5, lerp_thin);
+    }
+    return step;
+}
+
+// the fit's resampling (GaussianFitTask::Run, profilefit.cpp:191): as many entries as the profile has
+// samples, and both arrays kept -- d^2 as MPC_ResampleForUniformDistanceSquaredDistribution writes it
+__global__ void resample_fit_kernel(const float *d, const float *r, int nent, int nch, float *dsq_out, float *r_out) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)nent * nch) return;
+    const int ch = (int)(gid / nent), i = (int)(gid % nent);
+    const float *dc = d + (size_t)ch * nent, *rc = r + (size_t)ch * nent;
+    const float extent = dc[nent - 1];
+    const float q = (float)i * extent / (float)(nent - 1);
+    dsq_out[gid] = q;
+    r_out[gid] = resample_dev(dc, rc, (unsigned)nent, q);
+}
+
 unsigned round_up_pow2_u(unsigned v) {
     v--;
     v |= v >> 1; v |= v >> 2; v |= v >> 4; v |= v >> 8; v |= v >> 16;
@@ -307,29 +347,7 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
     // per-channel setup (channel_profile / layer_grid, material.cpp)
     std::vector<ChanSetup> cs(NC);
     std::vector<float> steps(NC);
-    for (int sc = 0; sc < NC; ++sc) {
-        float mfp_total = 0.f;
-        for (int l = 0; l < 2; ++l) mfp_total += 1.f / (lp.mua[l][sc] + lp.musp[l][sc]);
-        const float mfp = mfp_total / (float)2;
-        const float step = 12.f * mfp / (float)desired_length;
-        steps[sc] = step;
-        ChanSetup &c = cs[sc];
-        c.s2 = step * step;
-        c.nf = c.s2;
-        const float up[2] = {lp.eta[0], lp.eta[1] / lp.eta[0]}, lo[2] = {lp.eta[0] / lp.eta[1], lp.eta[1]};
-        for (int l = 0; l < 2; ++l) {
-            float thick = lp.thickness[l];
-            const float mua = lp.mua[l][sc], musp = lp.musp[l][sc];
-            const double mfp2 = 2. / (mua + musp);
-            double lerp = 1.;
-            if (lerp_thin) {
-                lerp = (thick < mfp2) ? (1. - exp(-thick * 2. / mfp2)) / (1. - exp(-2.)) : 1.;
-                if (thick < 0.01 * mfp2) thick = (float)(0.01 * mfp2);
-            }
-            c.lerp[l] = lerp;
-            for (int k = 0; k < kPairs; ++k) c.dip[l][k] = make_dipole(up[l], lo[l], thick, mua, musp, k - 5, lerp_thin);
-        }
-    }
+    for (int sc = 0; sc < NC; ++sc) steps[sc] = chan_setup(lp, sc, desired_length, lerp_thin, cs[sc]);
     const UniqueList &ul = unique_list((unsigned)ext);
     const int nent = (int)ul.nsq.size();
     const int tl = 2 * nent;
@@ -372,9 +390,10 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
                            d_cs.ptr + c0, nch, ext, M, grids.ptr);
         // forward 2-D transforms of all 4 grids
         hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * nch * 4)), dim3(256), M * sizeof(double2), stream,
-                           grids.ptr, M, logM, d_tw.ptr, 0);
+                           grids.ptr, M, logM, d_tw.ptr, 0, (size_t)0);
         hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
-                           (size_t)cols * M * sizeof(double2), stream, grids.ptr, M, logM, cols, d_tw.ptr, 0);
+                           (size_t)cols * M * sizeof(double2), stream, grids.ptr, M, logM, cols, d_tw.ptr, 0,
+                           (size_t)M * M);
         const int64_t freq = (int64_t)M * M * nch;
         hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, grids.ptr, nch,
                            M);
@@ -382,9 +401,9 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
         for (int ch = 0; ch < nch; ++ch) {
             double2 *g = grids.ptr + (size_t)ch * 4 * M * M;
             hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)M), dim3(256), M * sizeof(double2), stream, g, M, logM,
-                               d_tw.ptr, 1);
+                               d_tw.ptr, 1, (size_t)0);
             hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), 1u), dim3(256),
-                               (size_t)cols * M * sizeof(double2), stream, g, M, logM, cols, d_tw.ptr, 1);
+                               (size_t)cols * M * sizeof(double2), stream, g, M, logM, cols, d_tw.ptr, 1, (size_t)0);
         }
         hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((nent * nch + 255) / 256)), dim3(256), 0, stream, grids.ptr,
                            nch, M, d_ij.ptr, d_nsq.ptr, nent, d_step.ptr + c0, d_d.ptr + (size_t)c0 * nent,
@@ -415,6 +434,94 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
         out.rcp[c] = (float)(tl - 1) / last;
         out.total_reflectance[c] = (float)tot[c % NC];
     }
+}
+
+int fit_profile_samples(int desired_length) {
+    return (int)unique_list(round_up_pow2_u((unsigned)desired_length) - 1).nsq.size();
+}
+
+// GaussianFitTask::Run's profiles (profilefit.cpp:158-192) for n channels: the stages of build_profile_gpu
+// over batches of channels, the inverse transform of a batch's slot-0 grids folded into one rows and one
+// columns launch, the fit's resampling last.
+// prepare: every allocation and host copy (blocking), for all n channels; returns the batch size.
+int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, FitProfileWork &w) {
+    if (n < 1) throw Error(-1, "fit_profiles_prepare: no channels");
+    const int length = (int)round_up_pow2_u((unsigned)desired_length);
+    const int N = 2 * length, M = 2 * N;
+    int logM = 0;
+    while ((1 << logM) < M) ++logM;
+    if (desired_length < 2 || M > 4096) throw Error(-1, "fit_profiles_prepare: desired length outside 2..1024");
+    const int ext = length - 1;
+    std::vector<ChanSetup> cs((size_t)n);
+    std::vector<float> steps((size_t)n);
+    for (int i = 0; i < n; ++i) steps[i] = chan_setup(lp[i / NB], i % NB, desired_length, true, cs[i]);
+    const UniqueList &ul = unique_list((unsigned)ext);
+    const int nent = (int)ul.nsq.size();
+    std::vector<double2> tw(M / 2);
+    for (int k = 0; k < M / 2; ++k) {
+        const double ph = -2.0 * M_PI * (double)k / (double)M;
+        tw[k] = make_double2(cos(ph), sin(ph));
+    }
+    // batch: the workspace limit, the caller's cap, and the launch grids' limits (grid.y = 4 nch <= 65535)
+    const size_t grid_bytes = (size_t)M * M * sizeof(double2);
+    size_t batch = std::max<size_t>(1, ((size_t)8 << 30) / (4 * grid_bytes));
+    batch = std::min<size_t>(batch, 16383);
+    if (max_batch > 0) batch = std::min<size_t>(batch, (size_t)max_batch);
+    batch = std::min<size_t>(batch, (size_t)n);
+    w.tw.upload(tw.data(), tw.size());
+    w.setup.upload(reinterpret_cast<const unsigned char *>(cs.data()), cs.size() * sizeof(ChanSetup));
+    w.ij.upload(ul.ij.data(), ul.ij.size());
+    w.nsq.upload(ul.nsq.data(), ul.nsq.size());
+    w.step.upload(steps.data(), steps.size());
+    w.d.alloc(batch * nent);
+    w.r.alloc(batch * nent);
+    w.grids.alloc(batch * 4 * M * M);
+    w.n = n;
+    w.batch = (int)batch;
+    w.M = M;
+    w.logM = logM;
+    w.ext = ext;
+    w.nent = nent;
+    w.cols = std::max(1, std::min(4, 131072 / (M * (int)sizeof(double2))));
+    w.batches = 0;
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 w.cols * M * (int)sizeof(double2)));
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 M * (int)sizeof(double2)));
+    return w.batch;
+}
+
+// one batch: channels c0 .. c0 + nch - 1 (nch <= the prepared batch size) into dsq_dev / refl_dev [nch][nent].
+// Memset and kernels on `stream` only: nothing is allocated, copied from the host or waited for.
+void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitProfileWork &w, hipStream_t stream) {
+    if (nch < 1 || nch > w.batch || c0 < 0 || c0 + nch > w.n)
+        throw Error(-1, "fit_profiles_launch: range outside the prepared work");
+    const int M = w.M, logM = w.logM, ext = w.ext, nent = w.nent, cols = w.cols;
+    const size_t grid_bytes = (size_t)M * M * sizeof(double2);
+    const ChanSetup *d_cs = reinterpret_cast<const ChanSetup *>(w.setup.ptr);
+    const size_t chan_stride = (size_t)4 * M * M;
+    MPSS_HIP(hipMemsetAsync(w.grids.ptr, 0, (size_t)nch * 4 * grid_bytes, stream));
+    const int64_t cells = (int64_t)(ext + 1) * (ext + 1) * 2 * nch;
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, d_cs + c0, nch, ext,
+                       M, w.grids.ptr);
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 4), (unsigned)nch), dim3(256), M * sizeof(double2), stream,
+                       w.grids.ptr, M, logM, w.tw.ptr, 0, chan_stride);
+    hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
+                       (size_t)cols * M * sizeof(double2), stream, w.grids.ptr, M, logM, cols, w.tw.ptr, 0,
+                       (size_t)M * M);
+    const int64_t freq = (int64_t)M * M * nch;
+    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, w.grids.ptr, nch, M);
+    // inverse transform of every channel's R12 (slot 0): one rows launch, one columns launch
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)M, (unsigned)nch), dim3(256), M * sizeof(double2), stream,
+                       w.grids.ptr, M, logM, w.tw.ptr, 1, chan_stride);
+    hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)nch), dim3(256),
+                       (size_t)cols * M * sizeof(double2), stream, w.grids.ptr, M, logM, cols, w.tw.ptr, 1, chan_stride);
+    hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((nent * nch + 255) / 256)), dim3(256), 0, stream, w.grids.ptr,
+                       nch, M, w.ij.ptr, w.nsq.ptr, nent, w.step.ptr + c0, w.d.ptr, w.r.ptr);
+    hipLaunchKernelGGL(resample_fit_kernel, dim3((unsigned)(((int64_t)nent * nch + 255) / 256)), dim3(256), 0, stream,
+                       w.d.ptr, w.r.ptr, nent, nch, dsq_dev, refl_dev);
+    MPSS_HIP(hipGetLastError());
+    ++w.batches;
 }
 
 }  // namespace mpss

@@ -84,6 +84,15 @@ class Imagemap(C.Structure):
                 ("udelta", C.c_float), ("vdelta", C.c_float)]
 
 
+class ProfileFit(C.Structure):
+    """mpss_profilefit (Renderer "multipoleprofilefit" params, profilefit.cpp:524-558)."""
+    _fields_ = [("f_mel", C.POINTER(C.c_float)), ("f_eu", C.POINTER(C.c_float)), ("f_blood", C.POINTER(C.c_float)),
+                ("f_ohg", C.POINTER(C.c_float)), ("n_f_mel", C.c_uint32), ("n_f_eu", C.c_uint32),
+                ("n_f_blood", C.c_uint32), ("n_f_ohg", C.c_uint32), ("layer_thickness_nm", C.c_float * 2),
+                ("layer_ior", C.c_float * 2), ("desired_length", C.c_int), ("id_min", C.c_int), ("id_max", C.c_int),
+                ("max_profiles_per_batch", C.c_int)]
+
+
 def _sig(name, res, args):
     f = getattr(_lib, name)
     f.restype = res
@@ -146,6 +155,14 @@ _sig("mpss_host_skin_layers", C.c_int, [C.POINTER(LayeredSkin), f32p, f32p, f32p
 _sig("mpss_host_build_profile", C.c_int, [f32p, f32p, f32p, f32p, C.c_int, C.c_int, vp, u32p, vp, vp])
 _sig("mpss_host_rho_table", C.c_int, [C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, f32p, C.POINTER(C.c_float)])
 _sig("mpss_host_common_grid", C.c_int, [f32p, u32, f32p, C.c_int, C.c_int, vp, u32p] + [vp] * 11 + [C.POINTER(C.c_int)])
+_sig("mpss_profilefit_defaults", None, [C.POINTER(ProfileFit)])
+_sig("mpss_profilefit_params", C.c_int, [C.POINTER(ProfileFit), u32, f32p])
+_sig("mpss_profilefit_layers", C.c_int, [C.POINTER(ProfileFit), u32, f32p, f32p, f32p, f32p])
+_sig("mpss_profile_fit", C.c_int, [vp, C.POINTER(ProfileFit), u32p, u32p] + [vp] * 6 + [vp])
+_sig("mpss_host_profile_fit", C.c_int, [C.POINTER(ProfileFit), u32p, u32p] + [vp] * 5 + [u32p, vp, vp])
+_sig("mpss_sog_fit", C.c_int, [vp, u32, u32, f32p, f32p, u32, f32p, f32p, f32p] + [vp] * 5 + [vp])
+_sig("mpss_host_sog_fit", C.c_int, [u32, u32, f32p, f32p, u32, f32p, f32p, f32p] + [vp] * 6)
+_sig("mpss_host_sog_solve", C.c_int, [vp, vp, C.c_int, vp])
 _sig("mpss_host_octree_export", C.c_int, [u32, f32p, f32p, f32p, f32p, u32p] + [vp] * 8)
 
 
@@ -355,6 +372,147 @@ def host_octree_export(p, n, E, area):
     return d
 
 
+# ------------------------------------------------------------------ sum-of-Gaussians profile fit
+def profile_fit_spec(f_mel, f_eu, f_blood, f_ohg, layer_thickness_nm=None, layer_ior=None, desired_length=256,
+               id_range=(0, -1), max_profiles_per_batch=0):
+    """An mpss_profilefit for the four parameter ranges. Returns (struct, arrays it points at -- keep them
+    alive while the struct is used)."""
+    f = ProfileFit()
+    _lib.mpss_profilefit_defaults(C.byref(f))
+    keep = []
+    for name, vals in (("f_mel", f_mel), ("f_eu", f_eu), ("f_blood", f_blood), ("f_ohg", f_ohg)):
+        a = np.ascontiguousarray(np.atleast_1d(vals), np.float32)
+        keep.append(a)
+        setattr(f, name, a.ctypes.data_as(C.POINTER(C.c_float)))
+        setattr(f, "n_" + name, len(a))
+    if layer_thickness_nm is not None:
+        f.layer_thickness_nm = (C.c_float * 2)(*layer_thickness_nm)
+    if layer_ior is not None:
+        f.layer_ior = (C.c_float * 2)(*layer_ior)
+    f.desired_length = int(desired_length)
+    f.id_min, f.id_max = int(id_range[0]), int(id_range[1])
+    f.max_profiles_per_batch = int(max_profiles_per_batch)
+    return f, keep
+
+
+def _profile_fit_call(call):
+    """sizes first, then one full run; call(ns, ni, sigmas, coeffs, error, rgb, centre)"""
+    ns, ni = C.c_uint32(), C.c_uint32()
+    check(call(ns, ni, None, None, None, None, None))
+    sig = np.zeros(ns.value, np.float32)
+    out = dict(sigmas=sig, coeffs=np.zeros((ni.value, NB, ns.value), np.float32),
+               error=np.zeros((ni.value, NB), np.float32), rgb_coeffs=np.zeros((ni.value, 3, ns.value), np.float32),
+               centre=np.zeros((ni.value, NB), np.int32))
+    if ni.value == 0:
+        check(call(ns, ni, sig.ctypes.data, None, None, None, None))
+        return out
+    check(call(ns, ni, sig.ctypes.data, out["coeffs"].ctypes.data, out["error"].ctypes.data,
+               out["rgb_coeffs"].ctypes.data, out["centre"].ctypes.data))
+    return out
+
+
+def profilefit_params(fit, ident):
+    """ParamsFromId: (f_mel, f_eu, f_blood, f_ohg) of id `ident`; fit = profile_fit_spec(...)."""
+    out = np.zeros(4, np.float32)
+    check(_lib.mpss_profilefit_params(C.byref(fit[0]), ident, out))
+    return out
+
+
+def profilefit_layers(fit, ident):
+    """The layers of id `ident` in millimetres, as the fit builds them: mua, musp (2, 30), thickness, eta (2,)."""
+    mua = np.zeros((2, NB), np.float32)
+    musp = np.zeros((2, NB), np.float32)
+    th = np.zeros(2, np.float32)
+    eta = np.zeros(2, np.float32)
+    check(_lib.mpss_profilefit_layers(C.byref(fit[0]), ident, mua, musp, th, eta))
+    return mua, musp, th, eta
+
+
+def profilefit_mfp_bounds(fit, ids):
+    """Each channel's own mfp bounds (GaussianFitTask::Run, profilefit.cpp:165-173), float32: two arrays
+    (len(ids), 30) -- the candidate filter's mfpMin and mfpMax."""
+    lo, hi = [], []
+    for i in ids:
+        mua, musp, _, _ = profilefit_layers(fit, i)
+        mfp = np.float32(1) / (mua + musp)
+        lo.append(mfp.min(axis=0))
+        hi.append(mfp.max(axis=0))
+    return np.array(lo, np.float32), np.array(hi, np.float32)
+
+
+def host_profile_fit(fit, profiles=False):
+    """mpss_host_profile_fit: fit = profile_fit_spec(...). dict of sigmas, coeffs (ids, 30, n_sigmas), error
+    (ids, 30), rgb_coeffs (ids, 3, n_sigmas), centre (ids, 30); profiles=True adds dist_sq / data
+    (ids, 30, length), the resampled profiles the fit read (the same single run fills them)."""
+    f = fit[0]
+    L = fit_profile_length(f.desired_length) if profiles else 0
+    keep = {}
+
+    def call(ns, ni, s, c, e, r, ce):
+        d = y = None
+        if profiles and c is not None:
+            keep["dist_sq"] = np.zeros((ni.value, NB, L), np.float32)
+            keep["data"] = np.zeros((ni.value, NB, L), np.float32)
+            d, y = keep["dist_sq"].ctypes.data, keep["data"].ctypes.data
+        ln = C.c_uint32()
+        rc = _lib.mpss_host_profile_fit(C.byref(f), C.byref(ns), C.byref(ni), s, c, e, r, ce, C.byref(ln), d, y)
+        assert rc != 0 or d is None or ln.value == L
+        return rc
+
+    out = _profile_fit_call(call)
+    out.update(keep)
+    return out
+
+
+def fit_profile_length(desired_length):
+    """Samples of a profile at desired_length (the unique i^2 + j^2 <= ext^2, ext = the next power of two - 1;
+    MultipoleProfileCalculator.cpp:316-330): 87 at 16, 318 at 32, 1162 at 64, 15978 at 256."""
+    ext = 1
+    while ext < desired_length:
+        ext *= 2
+    ext -= 1
+    i = np.arange(ext + 1, dtype=np.int64)
+    n = (i[:, None] ** 2 + i[None, :] ** 2).ravel()
+    return len(np.unique(n[n <= ext * ext]))
+
+
+def _sog_args(dist_sq, data, sigmas, mfp_min, mfp_max):
+    d = np.ascontiguousarray(np.atleast_2d(dist_sq), np.float32)
+    y = np.ascontiguousarray(np.atleast_2d(data), np.float32)
+    assert d.shape == y.shape
+    n, L = d.shape
+    sig = np.ascontiguousarray(sigmas, np.float32)
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(mfp_min, np.float32), (n,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(mfp_max, np.float32), (n,)))
+    ns = len(sig)
+    out = dict(coeffs=np.zeros((n, ns), np.float32), error=np.zeros(n, np.float32), centre=np.zeros(n, np.int32),
+               cand_error=np.zeros((n, ns), np.float32), cand_coeffs=np.zeros((n, ns, 6), np.float32))
+    return (n, L, d, y, ns, sig, lo, hi), out
+
+
+def host_sog_fit(dist_sq, data, sigmas, mfp_min, mfp_max, gram=False):
+    """mpss_host_sog_fit: profiles (n, length) of d^2 and R -> dict of coeffs (n, n_sigmas), error, centre,
+    cand_error (n, n_sigmas; NaN: no candidate), cand_coeffs (n, n_sigmas, 6), and with gram=True cand_gram
+    (n, n_sigmas, 6, 6)."""
+    args, out = _sog_args(dist_sq, data, sigmas, mfp_min, mfp_max)
+    g = np.zeros((args[0], args[4], 6, 6), np.float64) if gram else None
+    check(_lib.mpss_host_sog_fit(*args, out["coeffs"].ctypes.data, out["error"].ctypes.data,
+                                 out["centre"].ctypes.data, out["cand_error"].ctypes.data,
+                                 out["cand_coeffs"].ctypes.data, g.ctypes.data if gram else None))
+    if gram:
+        out["cand_gram"] = g
+    return out
+
+
+def host_sog_solve(a, b, quirk=True):
+    """LinearSolve (gaussianfit.cpp:48-96) of the library for a 6 x 6 system."""
+    a = np.ascontiguousarray(a, np.float64).reshape(6, 6)
+    b = np.ascontiguousarray(b, np.float64).reshape(6)
+    x = np.zeros(6, np.float64)
+    check(_lib.mpss_host_sog_solve(a.ctypes.data, b.ctypes.data, int(quirk), x.ctypes.data))
+    return x
+
+
 # ------------------------------------------------------------------ device context
 class Context:
     """One MultipoleSubsurfaceIntegrator instance (multipolesubsurface.h:36-80) on one GPU."""
@@ -545,6 +703,28 @@ class Context:
         check(_lib.mpss_mc_profile(self.h, lay, len(lay), mfp_range, nsegments, nphotons, seed, r.ctypes.data,
                                    t.ctypes.data, C.byref(tr), C.byref(tt), C.byref(ev), stream))
         return dict(reflectance=r, transmittance=t, total_r=tr.value, total_t=tt.value, events=ev.value)
+
+    def profile_fit(self, fit, stream=None, timing=False):
+        """mpss_profile_fit: fit = profile_fit_spec(...); dict as host_profile_fit, with timing=True also
+        stage_ms = (profile stages, fit stages) by HIP events, summed over the batches, and batches = how many
+        batches of profiles ran."""
+        f = fit[0]
+        ms = (C.c_double * 3)()
+        out = _profile_fit_call(lambda ns, ni, s, c, e, r, ce: _lib.mpss_profile_fit(
+            self.h, C.byref(f), C.byref(ns), C.byref(ni), s, c, e, r, ce, C.addressof(ms) if timing else None,
+            stream))
+        if timing:
+            out["stage_ms"] = (ms[0], ms[1])
+            out["batches"] = int(ms[2])
+        return out
+
+    def sog_fit(self, dist_sq, data, sigmas, mfp_min, mfp_max, stream=None):
+        """mpss_sog_fit: the fit stage alone on host arrays (see host_sog_fit)."""
+        args, out = _sog_args(dist_sq, data, sigmas, mfp_min, mfp_max)
+        check(_lib.mpss_sog_fit(self.h, *args, out["coeffs"].ctypes.data, out["error"].ctypes.data,
+                                out["centre"].ctypes.data, out["cand_error"].ctypes.data,
+                                out["cand_coeffs"].ctypes.data, stream))
+        return out
 
     def replay_samples(self, spp, xres, yres):
         """The reference sampler's values over the sample extent: (yres+1, xres+1, spp', K) float32."""

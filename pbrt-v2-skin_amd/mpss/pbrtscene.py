@@ -160,7 +160,8 @@ class Scene:
         self.meshes = []     # dicts: P (world), N, S, uv, indices, o2w, w2o, reverse, material
         self.lights = []     # dicts: center, radius, L (rgb), nsamples; or kind="infinite", L, scale, l2w, w2l
         self.base_dir = "."
-        self.renderer = None  # ("mcprofile", ParamSet) when the file selects the MC profile renderer
+        self.renderer = None  # ("mcprofile", ParamSet) when the file selects the MC profile renderer;
+        #                       ("multipoleprofilefit", description dict) for the profile fit (tools/profilefit.py)
 
     def raster_to_camera(self):
         return camera_matrices(self.world_to_camera, self.fov, self.xres, self.yres, self.screen)
@@ -245,9 +246,12 @@ def load(path, **override):
                         raise ValueError("SurfaceIntegrator %r is outside this path" % cls)
                     sc.integrator = {k: v[1][0] for k, v in ps.items()}
                 elif d == "Renderer":
-                    if cls not in ("sampler", "mcprofile"):
+                    if cls == "multipoleprofilefit":
+                        sc.renderer = (cls, _profilefit_params(ps, base))
+                    elif cls not in ("sampler", "mcprofile"):
                         raise ValueError("Renderer %r is outside this path" % cls)
-                    sc.renderer = (cls, ps) if cls == "mcprofile" else None
+                    else:
+                        sc.renderer = (cls, ps) if cls == "mcprofile" else None
                 elif d in ("PixelFilter",):
                     if cls != "box" or ps.one("xwidth", 0.5) != 0.5 or ps.one("ywidth", 0.5) != 0.5:
                         raise ValueError("only the default 0.5-wide box filter is supported")
@@ -279,6 +283,31 @@ def load(path, **override):
     for k, v in override.items():
         setattr(sc, k, v)
     return sc
+
+
+def _profilefit_params(ps, base):
+    """CreateMultipoleProfileFitRenderer's parameters (renderers/profilefit.cpp:524-558) as the description
+    tools/profilefit.py runs: ranges (sorted, as FindParamRange), layers [(thickness_nm, ior)] * 2,
+    desired_length, id_range, filename (relative to the scene file)."""
+    if int(ps.one("splittasks", 0)):
+        raise ValueError("multipoleprofilefit: splittasks (writing split scenes and a .bat file, with a question "
+                         "on stdin) is not built here; pass an idrange per run instead")
+    ranges = {}
+    for k in ("f_mel", "f_eu", "f_blood", "f_ohg"):
+        v = ps.find(k)
+        if not v:
+            raise ValueError("multipoleprofilefit: param %s not specified" % k)
+        ranges[k] = sorted(float(x) for x in v)
+    lay = ps.find("layers")
+    if not lay or len(lay) < 4:
+        raise ValueError("multipoleprofilefit: \"skinlayer layers\" needs two (thickness, ior) pairs")
+    idr = ps.find("idrange")
+    filename = ps.one("filename", "")
+    if filename and not os.path.isabs(filename):
+        filename = os.path.join(base, filename)
+    return dict(ranges=ranges, layers=[(float(lay[0]), float(lay[1])), (float(lay[2]), float(lay[3]))],
+                desired_length=int(ps.one("desiredProfileLength", 256)),
+                id_range=(int(idr[0]), int(idr[1])) if idr and len(idr) == 2 else (0, -1), filename=filename)
 
 
 def _rgb3(v):
