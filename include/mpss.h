@@ -390,6 +390,31 @@ int mpss_mc_profile(mpss_ctx *ctx, const mpss_layer *layers, int nlayers, float 
 int mpss_mc_reference(const mpss_layer *layers, int nlayers, float mfp_range, int nsegments, int lerp_on_thin_slab,
                       double *reflectance, double *transmittance, double *total_r, double *total_t);
 
+/* ---- batched Monte-Carlo profiles (renderer "batchmcprofile", src/renderers/batchmcprofile.cpp) ---- */
+/* mpss_mc_profile for nslabs layer stacks (layers [nslabs][nlayers]) in one kernel launch: slab s is traced
+ * as mpss_mc_profile would trace it alone -- its own extent, nphotons photons, photon k of every slab on
+ * the stream (seed, k) -- so a slab's result differs from the single call's only in the order of the FP64
+ * tally sums. reflectance / transmittance [nslabs][nsegments] are nullable; with both null only the totals
+ * are tallied (per-lane sums, no ring memory). A tally counts under the same condition in both modes (the
+ * photon leaves inside the extent), so the totals mean the same. total_r / total_t [nslabs]; events
+ * (nullable) sums the batch. 1..65536 slabs, 1..8 layers, 1..4096 segments, musp > 0, mua >= 0,
+ * thickness > 0 in every slab; nphotons = 0 gives zeros. Synchronous on stream. */
+int mpss_mc_profile_batch(mpss_ctx *ctx, const mpss_layer *layers, int nslabs, int nlayers, float mfp_range,
+                          int nsegments, uint64_t nphotons, uint64_t seed, double *reflectance,
+                          double *transmittance, double *total_r, double *total_t, uint64_t *events, void *stream);
+/* mpss_mc_reference for nslabs layer stacks on the ctx's GPU (FP64 transforms): per slab the MPC at
+ * desired_length (the reference uses 1024; 2..1024, smaller lengths are for tests) with step
+ * (float)(extent * 1.01 / desired_length), R12 and T12, their unique-d^2 readout and totals, read at the
+ * ring centres. Slabs go through the transform workspace in batches of at most max_profiles_per_batch
+ * (0: as many as 8 GB hold; one slab takes 1 GiB at length 1024); results do not depend on it.
+ * The GPU builder combines two layers: with nlayers other than 2 every slab is computed by the host code
+ * of mpss_mc_reference instead (at desired_length). reflectance / transmittance are nullable.
+ * Synchronous on stream. */
+int mpss_mc_reference_batch(mpss_ctx *ctx, const mpss_layer *layers, int nslabs, int nlayers, float mfp_range,
+                            int nsegments, int desired_length, int lerp_on_thin_slab, int max_profiles_per_batch,
+                            double *reflectance, double *transmittance, double *total_r, double *total_t,
+                            void *stream);
+
 /* ---- sum-of-Gaussians profile fit (renderer "multipoleprofilefit", src/renderers/profilefit.cpp:158-379,
  * src/multipole/MultipoleProfileCalculator/gaussianfit.cpp:42-154) ---- */
 typedef struct {

@@ -545,12 +545,11 @@ void mpc_resample_distribution(const MpcOutput &in, int n, const float *points, 
 }
 
 // MultipoleReferenceTask::Run (renderers/mcprofile.cpp:381-425): the multipole profile of the
-// MC scene's layers at desiredLength 1024 with step extent * 1.01 / 1024, sampled at the ring
-// centres (i + .5) * extent / nSegments.
+// MC scene's layers at desiredLength 1024 (the reference's; `desired` lets tests run small grids) with
+// step extent * 1.01 / desired, sampled at the ring centres (i + .5) * extent / nSegments.
 void mc_reference_profile(const MpcLayer *layers, int n, double extent, int nsegments, bool lerp_thin, double *refl,
-                          double *trans, double *total_r, double *total_t) {
+                          double *trans, double *total_r, double *total_t, int desired) {
     MpcOutput o;
-    const int desired = 1024;
     mpc_compute(layers, n, (float)(extent * 1.01 / desired), desired, lerp_thin, o);
     *total_r = o.total_reflectance;
     *total_t = o.total_transmittance;

@@ -99,7 +99,14 @@ void mpc_compute(const MpcLayer *layers, int n, float step, int desired_length, 
 void mpc_resample_distribution(const MpcOutput &in, int n, const float *points, float *refl, float *trans);
 // MultipoleReferenceTask (mcprofile.cpp:381-425): ring-centre profile of the layers' multipole model
 void mc_reference_profile(const MpcLayer *layers, int n, double extent, int nsegments, bool lerp_on_thin_slab,
-                          double *refl, double *trans, double *total_r, double *total_t);
+                          double *refl, double *trans, double *total_r, double *total_t, int desired_length = 1024);
+// The same for nslabs two-layer stacks on the current HIP device (profile_gpu.hip): layers [nslabs][2],
+// extent [nslabs], outputs [nslabs][nsegments] (nullable) and [nslabs]. Slabs go through the transform
+// grids in batches of at most max_batch (0: as many as 8 GB of grids hold; one slab's four grids take
+// 1 GiB at desired_length 1024); a slab's result does not depend on the split. Synchronous on stream.
+void mc_reference_batch_gpu(const MpcLayer *layers, int nslabs, const double *extent, int nsegments,
+                            int desired_length, bool lerp_on_thin_slab, int max_batch, double *refl, double *trans,
+                            double *total_r, double *total_t, hipStream_t stream);
 
 // ComputeMonteCarloProfile's ring -> table conversion (multipole.cpp:328-355) for one band
 void profile_from_rings(const double *refl, int nseg, double extent, int target, std::vector<float> &table,

@@ -50,5 +50,11 @@ McScene make_mc_scene(const McLayer *layers, int n, double mfp_range, int nsegme
 // tallied fractions (photons exiting within the extent), events the free-flight count.
 void run_mc_profile(const McScene &sc, uint64_t nphotons, uint64_t seed, double *refl, double *trans,
                     double *total_r, double *total_t, uint64_t *events, hipStream_t stream);
+// The same walk for nslabs scenes (equal nsegments) in one kernel launch (mc_profile_batch.hip): nphotons
+// per slab, photon k of every slab on the stream (seed, k). refl / trans [nslabs][nsegments] are nullable;
+// with both null only the totals are tallied (no ring memory). totals [nslabs]; events sums the batch.
+constexpr int kMcMaxSlabs = 65536;
+void run_mc_profile_batch(const McScene *scenes, int nslabs, uint64_t nphotons, uint64_t seed, double *refl,
+                          double *trans, double *total_r, double *total_t, uint64_t *events, hipStream_t stream);
 
 }  // namespace mpss

@@ -582,6 +582,61 @@ int mpss_mc_reference(const mpss_layer *layers, int n, float mfp_range, int nseg
     });
 }
 
+int mpss_mc_profile_batch(mpss_ctx *c, const mpss_layer *layers, int nslabs, int n, float mfp_range, int nseg,
+                          uint64_t nphotons, uint64_t seed, double *refl, double *trans, double *tr, double *tt,
+                          uint64_t *events, void *stream) {
+    return guarded([&] {
+        require(c && layers && tr && tt, "mpss_mc_profile_batch: null argument");
+        require(nslabs >= 1 && nslabs <= kMcMaxSlabs, "mpss_mc_profile_batch: 1..65536 slabs supported");
+        // every slab is validated (as mpss_mc_profile validates its one) before the device is touched
+        std::vector<McScene> sc((size_t)nslabs);
+        for (int s = 0; s < nslabs; ++s)
+            sc[s] = make_mc_scene(reinterpret_cast<const McLayer *>(layers) + (size_t)s * std::max(n, 0), n,
+                                  (double)mfp_range, nseg);
+        Context &ctx = *reinterpret_cast<Context *>(c);
+        MPSS_HIP(hipSetDevice(ctx.config().device));
+        run_mc_profile_batch(sc.data(), nslabs, nphotons, seed, refl, trans, tr, tt, events, (hipStream_t)stream);
+    });
+}
+
+int mpss_mc_reference_batch(mpss_ctx *c, const mpss_layer *layers, int nslabs, int n, float mfp_range, int nseg,
+                            int desired_length, int lerp, int max_batch, double *refl, double *trans, double *tr,
+                            double *tt, void *stream) {
+    return guarded([&] {
+        require(c && layers && tr && tt, "mpss_mc_reference_batch: null argument");
+        require(nslabs >= 1 && nslabs <= kMcMaxSlabs, "mpss_mc_reference_batch: 1..65536 slabs supported");
+        require(n >= 1 && n <= 8 && nseg >= 1 && nseg <= (1 << 16), "mpss_mc_reference_batch: bad layer or ring count");
+        require(desired_length >= 2 && desired_length <= 1024, "mpss_mc_reference_batch: desired length outside 2..1024");
+        std::vector<MpcLayer> ml((size_t)nslabs * n);
+        std::vector<double> extent((size_t)nslabs);
+        for (int s = 0; s < nslabs; ++s) {
+            double mfp_total = 0.;
+            for (int i = 0; i < n; ++i) {
+                const mpss_layer &l = layers[(size_t)s * n + i];
+                require(l.musp > 0.f && l.mua >= 0.f && l.thickness > 0.f,
+                        "mpss_mc_reference_batch: layers need musp > 0, mua >= 0, thickness > 0");
+                ml[(size_t)s * n + i] = MpcLayer{l.mua, l.musp, l.ior, l.thickness};
+                mfp_total += 1. / (double)(l.mua + l.musp);  // Render, mcprofile.cpp:457-463
+            }
+            extent[s] = mfp_range * (mfp_total / (double)n);
+        }
+        if (n != 2) {  // the GPU builder combines two layers; other stacks take the host path, slab by slab
+            std::vector<double> r((size_t)nseg), t((size_t)nseg);
+            for (int s = 0; s < nslabs; ++s) {
+                mc_reference_profile(&ml[(size_t)s * n], n, extent[s], nseg, lerp != 0, r.data(), t.data(), tr + s,
+                                     tt + s, desired_length);
+                if (refl) std::copy(r.begin(), r.end(), refl + (size_t)s * nseg);
+                if (trans) std::copy(t.begin(), t.end(), trans + (size_t)s * nseg);
+            }
+            return;
+        }
+        Context &ctx = *reinterpret_cast<Context *>(c);
+        MPSS_HIP(hipSetDevice(ctx.config().device));
+        mc_reference_batch_gpu(ml.data(), nslabs, extent.data(), nseg, desired_length, lerp != 0, max_batch, refl,
+                               trans, tr, tt, (hipStream_t)stream);
+    });
+}
+
 int mpss_host_tessellate(uint32_t nv, const float *P, const float *N, const float *S, const float *uv, uint32_t nt,
                          const int32_t *idx, const float *o2w, const float *w2o, int flip, uint32_t mat,
                          float min_dist, int incenter, void *rec, uint32_t *n) {

@@ -12,6 +12,9 @@
 //                      loop order wins (:316-330)
 //   total_kernel       Kahan sum of the R12 grid (totalReflectance)
 //   resample_kernel    uniform-d^2 resampling to twice the sample count (:355-426)
+// mc_reference_batch_gpu runs the same stages for the Monte-Carlo renderers' multipole references
+// (MultipoleReferenceTask::Run, renderers/mcprofile.cpp:381-425): the combine also writes T12, both
+// grids come back to the time domain, and ring_resample_kernel reads them at the ring centres.
 // FP64 throughout the grids and transforms, like the reference's MPC; results agree with the
 // host build (and the kissfft-based oracle) to FP64 rounding of differently ordered FFTs.
 #include <algorithm>
@@ -164,8 +167,9 @@ __global__ __launch_bounds__(256) void fft_cols_kernel(double2 *data, int M, int
     }
 }
 
-// R12 into slot 0 of each channel (CombineLayerProfiles, MultipoleProfileCalculator.cpp:253-280)
-__global__ void combine_kernel(double2 *grids, int nch, int M) {
+// R12 into slot 0 of each channel (CombineLayerProfiles, MultipoleProfileCalculator.cpp:253-280);
+// with_t: also T12 = T1 T2 / (1 - R2 R1) into slot 1
+__global__ void combine_kernel(double2 *grids, int nch, int M, int with_t) {
     const int64_t mm = (int64_t)M * M;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= mm * nch) return;
@@ -175,6 +179,7 @@ __global__ void combine_kernel(double2 *grids, int nch, int M) {
     const double2 fR1 = g[k], fT1 = g[mm + k], fR2 = g[2 * mm + k];
     const double2 one = csub(make_double2(1., 0.), cmul(fR2, fR1));
     g[k] = cadd(cdiv(cmul(cmul(fT1, fR2), fT1), one), fR1);
+    if (with_t) g[mm + k] = cdiv(cmul(fT1, g[3 * mm + k]), one);
 }
 
 // unique d^2 entries: value = Re(R12)(i, j) / M^2 as float * 1 / step^2
@@ -192,11 +197,13 @@ __global__ void readout_kernel(const double2 *grids, int nch, int M, const int2 
     d_out[gid] = (float)nsq[k] * st * st;
 }
 
-// totalReflectance = Kahan sum over the N x N time-domain grid (numutil.h:236-246), per channel
-__global__ __launch_bounds__(256) void total_kernel(const double2 *grids, int M, int N, double *out) {
+// totalReflectance = Kahan sum over the N x N time-domain grid (numutil.h:236-246), per channel; slot 1 holds
+// T12 where the combine wrote it (totalTransmittance). out[ch * out_stride]
+__global__ __launch_bounds__(256) void total_kernel(const double2 *grids, int M, int N, int slot, double *out,
+                                                    int out_stride) {
     __shared__ double part[256];
     const int ch = blockIdx.x;
-    const double2 *R = grids + (size_t)ch * 4 * M * M;
+    const double2 *R = grids + ((size_t)ch * 4 + slot) * M * M;
     const double s = 1.0 / ((double)M * (double)M);
     const int c = (N - 1) / 2;
     double sum = 0., comp = 0.;
@@ -216,7 +223,7 @@ __global__ __launch_bounds__(256) void total_kernel(const double2 *grids, int M,
             cp = (t - tot) - y;
             tot = t;
         }
-        out[ch] = tot;
+        out[(size_t)ch * out_stride] = tot;
     }
 }
 
@@ -289,18 +296,15 @@ const UniqueList &unique_list(unsigned ext) {
     return u;
 }
 
-// per-channel setup (channel_profile / layer_grid, material.cpp); returns the channel's step
-float chan_setup(const LayerParams &lp, int sc, int desired_length, bool lerp_thin, ChanSetup &c) {
-    float mfp_total = 0.f;
-    for (int l = 0; l < 2; ++l) mfp_total += 1.f / (lp.mua[l][sc] + lp.musp[l][sc]);
-    const float mfp = mfp_total / (float)2;
-    const float step = 12.f * mfp / (float)desired_length;
+// the grid fill's constants for two layers at a given step (layer_grid, material.cpp; the Fresnel ratios
+// as MPC_ComputeDiffusionProfile passes them, :294-314)
+void two_layer_setup(const MpcLayer L[2], float step, bool lerp_thin, ChanSetup &c) {
     c.s2 = step * step;
     c.nf = c.s2;
-    const float up[2] = {lp.eta[0], lp.eta[1] / lp.eta[0]}, lo[2] = {lp.eta[0] / lp.eta[1], lp.eta[1]};
+    const float up[2] = {L[0].ior, L[1].ior / L[0].ior}, lo[2] = {L[0].ior / L[1].ior, L[1].ior};
     for (int l = 0; l < 2; ++l) {
-        float thick = lp.thickness[l];
-        const float mua = lp.mua[l][sc], musp = lp.musp[l][sc];
+        float thick = L[l].thickness;
+        const float mua = L[l].mua, musp = L[l].musp;
         const double mfp2 = 2. / (mua + musp);
         double lerp = 1.;
         if (lerp_thin) {
@@ -310,6 +314,17 @@ float chan_setup(const LayerParams &lp, int sc, int desired_length, bool lerp_th
         c.lerp[l] = lerp;
         for (int k = 0; k < kPairs; ++k) c.dip[l][k] = make_dipole(up[l], lo[l], thick, mua, musp, k - 5, lerp_thin);
     }
+}
+
+// per-channel setup (channel_profile / layer_grid, material.cpp); returns the channel's step
+float chan_setup(const LayerParams &lp, int sc, int desired_length, bool lerp_thin, ChanSetup &c) {
+    float mfp_total = 0.f;
+    for (int l = 0; l < 2; ++l) mfp_total += 1.f / (lp.mua[l][sc] + lp.musp[l][sc]);
+    const float mfp = mfp_total / (float)2;
+    const float step = 12.f * mfp / (float)desired_length;
+    const MpcLayer L[2] = {{lp.mua[0][sc], lp.musp[0][sc], lp.eta[0], lp.thickness[0]},
+                           {lp.mua[1][sc], lp.musp[1][sc], lp.eta[1], lp.thickness[1]}};
+    two_layer_setup(L, step, lerp_thin, c);
     return step;
 }
 
@@ -324,6 +339,21 @@ __global__ void resample_fit_kernel(const float *d, const float *r, int nent, in
     const float q = (float)i * extent / (float)(nent - 1);
     dsq_out[gid] = q;
     r_out[gid] = resample_dev(dc, rc, (unsigned)nent, q);
+}
+
+// MPC_ResampleDistribution (MultipoleProfileCalculator.cpp:429-449) at the MC profile's ring centres
+// (MultipoleReferenceTask::Run, mcprofile.cpp:405-413): point = (float)((i + .5) * (extent / nseg)),
+// d^2 = point * point in float; R and T of slab ch into out_r / out_t [nch][nseg] as doubles
+__global__ void ring_resample_kernel(const float *d, const float *r, const float *t, int nent, int nch,
+                                     const double *extent, int nseg, double *out_r, double *out_t) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (int64_t)nseg * nch) return;
+    const int ch = (int)(gid / nseg), i = (int)(gid % nseg);
+    const float *dc = d + (size_t)ch * nent;
+    const float point = (float)((i + .5) * (extent[ch] / nseg));
+    const float dsq = point * point;
+    out_r[gid] = resample_dev(dc, r + (size_t)ch * nent, (unsigned)nent, dsq);
+    out_t[gid] = resample_dev(dc, t + (size_t)ch * nent, (unsigned)nent, dsq);
 }
 
 unsigned round_up_pow2_u(unsigned v) {
@@ -396,7 +426,7 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
                            (size_t)M * M);
         const int64_t freq = (int64_t)M * M * nch;
         hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, grids.ptr, nch,
-                           M);
+                           M, 0);
         // inverse transform of R12 (slot 0 of each channel): rows of the slot-0 matrices only
         for (int ch = 0; ch < nch; ++ch) {
             double2 *g = grids.ptr + (size_t)ch * 4 * M * M;
@@ -408,7 +438,8 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
         hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((nent * nch + 255) / 256)), dim3(256), 0, stream, grids.ptr,
                            nch, M, d_ij.ptr, d_nsq.ptr, nent, d_step.ptr + c0, d_d.ptr + (size_t)c0 * nent,
                            d_r.ptr + (size_t)c0 * nent);
-        hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, grids.ptr, M, N, d_tot.ptr + c0);
+        hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, grids.ptr, M, N, 0,
+                           d_tot.ptr + c0, 1);
         MPSS_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((tl * NC + 255) / 256)), dim3(256), 0, stream, d_d.ptr,
@@ -510,7 +541,8 @@ void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitPr
                        (size_t)cols * M * sizeof(double2), stream, w.grids.ptr, M, logM, cols, w.tw.ptr, 0,
                        (size_t)M * M);
     const int64_t freq = (int64_t)M * M * nch;
-    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, w.grids.ptr, nch, M);
+    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, w.grids.ptr, nch, M,
+                       0);
     // inverse transform of every channel's R12 (slot 0): one rows launch, one columns launch
     hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)M, (unsigned)nch), dim3(256), M * sizeof(double2), stream,
                        w.grids.ptr, M, logM, w.tw.ptr, 1, chan_stride);
@@ -522,6 +554,113 @@ void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitPr
                        w.d.ptr, w.r.ptr, nent, nch, dsq_dev, refl_dev);
     MPSS_HIP(hipGetLastError());
     ++w.batches;
+}
+
+// MultipoleReferenceTask::Run (renderers/mcprofile.cpp:381-425) for nslabs two-layer stacks: what
+// mc_reference_profile (material.cpp) computes on the host, with the stages of fit_profiles_launch over
+// batches of slabs. Beyond the fit's profile: the step is (float)(extent * 1.01 / desired_length), the
+// combine writes T12 beside R12, both come back to the time domain, both are read out and Kahan-summed,
+// and the profile is read at the ring centres. A slab's grids are its own, so its result does not depend
+// on the batch size. Every allocation and upload happens before the first launch; one wait at the end.
+void mc_reference_batch_gpu(const MpcLayer *layers, int nslabs, const double *extent, int nsegments,
+                            int desired_length, bool lerp_thin, int max_batch, double *refl, double *trans,
+                            double *total_r, double *total_t, hipStream_t stream) {
+    if (nslabs < 1) throw Error(-1, "mc_reference_batch: no slabs");
+    const int length = (int)round_up_pow2_u((unsigned)desired_length);
+    const int N = 2 * length, M = 2 * N;
+    int logM = 0;
+    while ((1 << logM) < M) ++logM;
+    if (desired_length < 2 || M > 4096) throw Error(-1, "mc_reference_batch: desired length outside 2..1024");
+    const int ext = length - 1;
+    std::vector<ChanSetup> cs((size_t)nslabs);
+    std::vector<float> steps((size_t)nslabs);
+    for (int s = 0; s < nslabs; ++s) {
+        steps[s] = (float)(extent[s] * 1.01 / desired_length);
+        two_layer_setup(layers + 2 * (size_t)s, steps[s], lerp_thin, cs[s]);
+    }
+    const UniqueList &ul = unique_list((unsigned)ext);
+    const int nent = (int)ul.nsq.size();
+    std::vector<double2> tw(M / 2);
+    for (int k = 0; k < M / 2; ++k) {
+        const double ph = -2.0 * M_PI * (double)k / (double)M;
+        tw[k] = make_double2(cos(ph), sin(ph));
+    }
+    // batch: the workspace limit (8 GB of grids; 1 GiB per slab at M = 4096), the caller's cap, and the
+    // launch grids' limits (grid.y = 4 nch <= 65535)
+    const size_t mm = (size_t)M * M, grid_bytes = mm * sizeof(double2);
+    size_t batch = std::max<size_t>(1, ((size_t)8 << 30) / (4 * grid_bytes));
+    batch = std::min<size_t>(batch, 16383);
+    if (max_batch > 0) batch = std::min<size_t>(batch, (size_t)max_batch);
+    batch = std::min<size_t>(batch, (size_t)nslabs);
+    DevBuf<double2> d_tw, grids;
+    DevBuf<ChanSetup> d_cs;
+    DevBuf<int2> d_ij;
+    DevBuf<uint32_t> d_nsq;
+    DevBuf<float> d_step, d_d, d_r, d_t;
+    DevBuf<double> d_ext, d_out;  // d_out: rings R [nslabs][nseg], rings T, then totals [nslabs][2]
+    d_tw.upload(tw.data(), tw.size());
+    d_cs.upload(cs.data(), cs.size());
+    d_ij.upload(ul.ij.data(), ul.ij.size());
+    d_nsq.upload(ul.nsq.data(), ul.nsq.size());
+    d_step.upload(steps.data(), steps.size());
+    d_ext.upload(extent, (size_t)nslabs);
+    d_d.alloc(batch * nent);
+    d_r.alloc(batch * nent);
+    d_t.alloc(batch * nent);
+    grids.alloc(batch * 4 * mm);
+    const size_t nring = (size_t)nslabs * nsegments;
+    d_out.alloc(2 * nring + 2 * (size_t)nslabs);
+    double *o_r = d_out.ptr, *o_t = o_r + nring, *o_tot = o_t + nring;
+    const int cols = std::max(1, std::min(4, 131072 / (M * (int)sizeof(double2))));
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 cols * M * (int)sizeof(double2)));
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 M * (int)sizeof(double2)));
+    const size_t chan_stride = 4 * mm;
+    for (int c0 = 0; c0 < nslabs; c0 += (int)batch) {
+        const int nch = std::min((int)batch, nslabs - c0);
+        MPSS_HIP(hipMemsetAsync(grids.ptr, 0, (size_t)nch * 4 * grid_bytes, stream));
+        const int64_t cells = (int64_t)(ext + 1) * (ext + 1) * 2 * nch;
+        hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, d_cs.ptr + c0,
+                           nch, ext, M, grids.ptr);
+        hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 4), (unsigned)nch), dim3(256), M * sizeof(double2),
+                           stream, grids.ptr, M, logM, d_tw.ptr, 0, chan_stride);
+        hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
+                           (size_t)cols * M * sizeof(double2), stream, grids.ptr, M, logM, cols, d_tw.ptr, 0, mm);
+        const int64_t freq = (int64_t)mm * nch;
+        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, grids.ptr, nch, M,
+                           1);
+        // inverse transforms of R12 (slot 0) and T12 (slot 1): the two slots are adjacent, so one rows launch
+        // covers both; the columns go slot by slot
+        hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 2), (unsigned)nch), dim3(256), M * sizeof(double2),
+                           stream, grids.ptr, M, logM, d_tw.ptr, 1, chan_stride);
+        for (int slot = 0; slot < 2; ++slot)
+            hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)nch), dim3(256),
+                               (size_t)cols * M * sizeof(double2), stream, grids.ptr + slot * mm, M, logM, cols, d_tw.ptr,
+                               1, chan_stride);
+        // the readout takes a channel's grid at grids + ch * 4 M^2: offset by one grid it reads T12
+        const unsigned rb = (unsigned)(((int64_t)nent * nch + 255) / 256);
+        hipLaunchKernelGGL(readout_kernel, dim3(rb), dim3(256), 0, stream, grids.ptr, nch, M, d_ij.ptr, d_nsq.ptr, nent,
+                           d_step.ptr + c0, d_d.ptr, d_r.ptr);
+        hipLaunchKernelGGL(readout_kernel, dim3(rb), dim3(256), 0, stream, grids.ptr + mm, nch, M, d_ij.ptr, d_nsq.ptr,
+                           nent, d_step.ptr + c0, d_d.ptr, d_t.ptr);
+        for (int slot = 0; slot < 2; ++slot)
+            hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, grids.ptr, M, N, slot,
+                               o_tot + 2 * (size_t)c0 + slot, 2);
+        hipLaunchKernelGGL(ring_resample_kernel, dim3((unsigned)(((int64_t)nsegments * nch + 255) / 256)), dim3(256), 0,
+                           stream, d_d.ptr, d_r.ptr, d_t.ptr, nent, nch, d_ext.ptr + c0, nsegments,
+                           o_r + (size_t)c0 * nsegments, o_t + (size_t)c0 * nsegments);
+        MPSS_HIP(hipGetLastError());
+    }
+    std::vector<double> tot(2 * (size_t)nslabs);
+    if (refl) MPSS_HIP(hipMemcpyAsync(refl, o_r, sizeof(double) * nring, hipMemcpyDeviceToHost, stream));
+    if (trans) MPSS_HIP(hipMemcpyAsync(trans, o_t, sizeof(double) * nring, hipMemcpyDeviceToHost, stream));
+    MPSS_HIP(hipMemcpyAsync(tot.data(), o_tot, sizeof(double) * tot.size(), hipMemcpyDeviceToHost, stream));
+    MPSS_HIP(hipStreamSynchronize(stream));
+    for (int s = 0; s < nslabs; ++s) {  // MPC_Output's totals are floats
+        total_r[s] = (float)tot[2 * (size_t)s];
+        total_t[s] = (float)tot[2 * (size_t)s + 1];
+    }
 }
 
 }  // namespace mpss

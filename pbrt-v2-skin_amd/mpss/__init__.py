@@ -143,6 +143,10 @@ _sig("mpss_mc_reference", C.c_int, [f32p, C.c_int, C.c_float, C.c_int, C.c_int, 
                                     C.POINTER(C.c_double)])
 _sig("mpss_mc_profile", C.c_int, [vp, f32p, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, vp, vp,
                                   C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), vp])
+_sig("mpss_mc_profile_batch", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, vp, vp,
+                                        vp, vp, C.POINTER(C.c_uint64), vp])
+_sig("mpss_mc_reference_batch", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          vp, vp, vp, vp, vp])
 _sig("mpss_host_tessellate", C.c_int, [u32, f32p, vp, vp, vp, u32, C.POINTER(C.c_int32), f32p, f32p, C.c_int, u32,
                                        C.c_float, C.c_int, vp, u32p])
 _sig("mpss_imagemap_defaults", None, [C.POINTER(Imagemap)])
@@ -312,6 +316,14 @@ def mc_reference(layers, mfp_range=16.0, nsegments=1024, lerp=True):
     check(_lib.mpss_mc_reference(lay, len(lay), mfp_range, nsegments, int(lerp), r.ctypes.data, t.ctypes.data,
                                  C.byref(tr), C.byref(tt)))
     return dict(reflectance=r, transmittance=t, total_r=tr.value, total_t=tt.value)
+
+
+def mc_extent(layers, mfp_range=16.0):
+    """The MC profile's tally radius per slab (Render, mcprofile.cpp:457-463): mfp_range x the mean over
+    layers of 1 / (mua + musp), the sum in float, the rest in double. layers [S, n, 4] -> [S]."""
+    lay = np.asarray(layers, np.float32)
+    mfp = (1.0 / (lay[..., 0] + lay[..., 1]).astype(np.float64)).sum(axis=-1) / lay.shape[-2]
+    return float(np.float32(mfp_range)) * mfp
 
 
 def host_dipole_rd(sigma_a, sigmap_s, eta, d2):
@@ -703,6 +715,40 @@ class Context:
         check(_lib.mpss_mc_profile(self.h, lay, len(lay), mfp_range, nsegments, nphotons, seed, r.ctypes.data,
                                    t.ctypes.data, C.byref(tr), C.byref(tt), C.byref(ev), stream))
         return dict(reflectance=r, transmittance=t, total_r=tr.value, total_t=tt.value, events=ev.value)
+
+    def mc_profile_batch(self, layers, mfp_range=16.0, nsegments=1024, nphotons=100, seed=89, rings=True,
+                         stream=None):
+        """mpss_mc_profile_batch: layers [S, n, 4], every slab traced as mc_profile traces it alone, in one
+        kernel launch. rings=False tallies the totals only (reflectance / transmittance are None).
+        Arrays carry a leading slab axis; extent [S] is each slab's tally radius; events sums the batch."""
+        lay = np.ascontiguousarray(layers, np.float32)
+        if lay.ndim != 3 or lay.shape[2] != 4:
+            raise ValueError("mc_profile_batch: layers must be [slabs, layers, 4]")
+        S, n = lay.shape[0], lay.shape[1]
+        r = np.zeros((S, nsegments), np.float64) if rings else None
+        t = np.zeros((S, nsegments), np.float64) if rings else None
+        tr, tt, ev = np.zeros(S, np.float64), np.zeros(S, np.float64), C.c_uint64()
+        check(_lib.mpss_mc_profile_batch(self.h, lay.ctypes.data, S, n, mfp_range, nsegments, nphotons, seed,
+                                         r.ctypes.data if rings else None, t.ctypes.data if rings else None,
+                                         tr.ctypes.data, tt.ctypes.data, C.byref(ev), stream))
+        return dict(reflectance=r, transmittance=t, total_r=tr, total_t=tt, extent=mc_extent(lay, mfp_range),
+                    events=ev.value)
+
+    def mc_reference_batch(self, layers, mfp_range=16.0, nsegments=1024, lerp=True, desired_length=1024,
+                           max_profiles_per_batch=0, stream=None):
+        """mpss_mc_reference_batch: mc_reference for layers [S, n, 4] on the GPU (two-layer slabs; other
+        layer counts run the host code per slab). The dict of mc_reference with a leading slab axis."""
+        lay = np.ascontiguousarray(layers, np.float32)
+        if lay.ndim != 3 or lay.shape[2] != 4:
+            raise ValueError("mc_reference_batch: layers must be [slabs, layers, 4]")
+        S, n = lay.shape[0], lay.shape[1]
+        r = np.zeros((S, nsegments), np.float64)
+        t = np.zeros((S, nsegments), np.float64)
+        tr, tt = np.zeros(S, np.float64), np.zeros(S, np.float64)
+        check(_lib.mpss_mc_reference_batch(self.h, lay.ctypes.data, S, n, mfp_range, nsegments, desired_length,
+                                           int(lerp), max_profiles_per_batch, r.ctypes.data, t.ctypes.data,
+                                           tr.ctypes.data, tt.ctypes.data, stream))
+        return dict(reflectance=r, transmittance=t, total_r=tr, total_t=tt)
 
     def profile_fit(self, fit, stream=None, timing=False):
         """mpss_profile_fit: fit = profile_fit_spec(...); dict as host_profile_fit, with timing=True also

@@ -160,7 +160,7 @@ class Scene:
         self.meshes = []     # dicts: P (world), N, S, uv, indices, o2w, w2o, reverse, material
         self.lights = []     # dicts: center, radius, L (rgb), nsamples; or kind="infinite", L, scale, l2w, w2l
         self.base_dir = "."
-        self.renderer = None  # ("mcprofile", ParamSet) when the file selects the MC profile renderer;
+        self.renderer = None  # ("mcprofile" or "batchmcprofile", ParamSet) for the MC profile renderers;
         #                       ("multipoleprofilefit", description dict) for the profile fit (tools/profilefit.py)
 
     def raster_to_camera(self):
@@ -248,10 +248,10 @@ def load(path, **override):
                 elif d == "Renderer":
                     if cls == "multipoleprofilefit":
                         sc.renderer = (cls, _profilefit_params(ps, base))
-                    elif cls not in ("sampler", "mcprofile"):
+                    elif cls not in ("sampler", "mcprofile", "batchmcprofile"):
                         raise ValueError("Renderer %r is outside this path" % cls)
                     else:
-                        sc.renderer = (cls, ps) if cls == "mcprofile" else None
+                        sc.renderer = (cls, ps) if cls != "sampler" else None
                 elif d in ("PixelFilter",):
                     if cls != "box" or ps.one("xwidth", 0.5) != 0.5 or ps.one("ywidth", 0.5) != 0.5:
                         raise ValueError("only the default 0.5-wide box filter is supported")
