@@ -48,24 +48,34 @@ void skin_fit_layer_params(float f_mel, float f_eu, float f_blood, float f_ohg, 
 void skin_fit_mfp_range(float f_mel, float f_eu, float f_blood, float f_ohg, float &mfp_min, float &mfp_max);
 void fit_channel_profile(const LayerParams &lp, int sc, int desired_length, std::vector<float> &dsq,
                          std::vector<float> &refl);
-// The same profiles for n channels on the current HIP device (profile_gpu.hip). lp[i / NB] band i % NB is
-// channel i. Channels go through the transform grids in batches of at most max_batch (0: as many as 8 GB of
-// grids hold); a channel's result does not depend on the split. fit_profiles_prepare does every allocation
-// and (blocking) host copy for all n channels and returns the batch size; fit_profiles_launch queues one
-// batch (channels c0 .. c0 + nch - 1, nch <= the batch size) on `stream` -- a memset and kernels only -- and
-// writes its d^2 and R to dsq_dev / refl_dev [nch][fit_profile_samples(desired_length)].
-struct FitProfileWork {  // the builder's device workspace: keep it alive until the stream has run the work
+// The grid pipeline of the GPU multipole builders (profile_gpu.hip): every channel takes four M x M complex
+// FP64 transform grids, and the channels go through them `batch` at a time.
+struct GridPlan {
+    int length, N, M, logM, ext;  // desired_length rounded up to a power of two, N = 2 length, M = 2 N, ext = length - 1
+    int nent, cols, batch;  // a profile's unique d^2 samples; columns per workgroup of the column transform; batch size
+};
+struct ChanSetup;  // the grid fill's constants of one channel (profile_gpu.hip)
+// The pipeline's device workspace. It must outlive the work queued on the stream: the fit path returns from
+// its launches with the work still queued (the caller's hipStreamSynchronize ends it); build_profile_gpu and
+// mc_reference_batch_gpu synchronise before they return.
+struct GridWork {
+    GridPlan plan;
     DevBuf<double2> grids, tw;
-    DevBuf<unsigned char> setup;
+    DevBuf<ChanSetup> setup;  // [n]
     DevBuf<int2> ij;
     DevBuf<uint32_t> nsq;
-    DevBuf<float> step, d, r;
-    int n = 0, batch = 0, M = 0, logM = 0, ext = 0, nent = 0, cols = 0;
-    int batches = 0;  // launches so far
+    DevBuf<float> step;     // [n]
+    DevBuf<float> d, r, t;  // a batch's unique-d^2 samples [batch][nent]; t only where T12 is wanted
+    int n = 0;              // channels prepared
+    int batches = 0;        // batches launched so far
 };
-int fit_profile_samples(int desired_length);
-int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, FitProfileWork &work);
-void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitProfileWork &work, hipStream_t stream);
+// fit_channel_profile for n channels on the current HIP device: lp[i / NB] band i % NB is channel i, in
+// batches of at most max_batch (0: as many as 8 GB of grids hold); a channel's result does not depend on the
+// split. fit_profiles_prepare does every allocation and (blocking) host copy and returns the batch size;
+// fit_profiles_launch queues one batch (channels c0 .. c0 + nch - 1, nch <= the batch size) on `stream` -- a
+// memset and kernels only -- and writes its d^2 and R to dsq_dev / refl_dev [nch][work.plan.nent].
+int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, GridWork &work);
+void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, GridWork &work, hipStream_t stream);
 // distinct: channels 0..distinct-1 are built and channel c >= distinct copies channel c % distinct
 // (rgbprofile: lp's band c already holds component c % 3, so 3 builds give all 30 rows)
 void build_profile(const LayerParams &lp, int desired_length, bool lerp_on_thin_slab, ProfileTables &out,

@@ -1,7 +1,5 @@
 // mpss_abi.cpp -- the extern "C" boundary of libmpss (include/mpss.h).
 #include <algorithm>
-#include <atomic>
-#include <thread>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -15,6 +13,7 @@
 #include "mc_profile.h"
 #include "mo_kernel.h"
 #include "profile_fit.h"
+#include "profile_fit_driver.h"
 #include "sog_fit.h"
 #include "spectral.h"
 
@@ -47,89 +46,39 @@ void require(bool ok, const char *msg) {
     if (!ok) throw Error(MPSS_ERR_INVALID, msg);
 }
 
-// DoProfileFit's setup (profilefit.cpp:284-312): sorted ranges, the sigma list over the whole grid, the
-// clipped id range
-struct FitPlan {
-    std::vector<float> range[4];
-    uint32_t n[4];
-    uint32_t total = 0, id0 = 0, id1 = 0;
-    std::vector<float> sigmas;
-    void params(uint32_t id, float out[4]) const {
-        const float *const r[4] = {range[0].data(), range[1].data(), range[2].data(), range[3].data()};
-        fit_params_from_id(id, r, n, out);
-    }
-};
-
-FitPlan make_fit_plan(const mpss_profilefit &f, bool with_sigmas = true) {
-    FitPlan pl;
-    const float *src[4] = {f.f_mel, f.f_eu, f.f_blood, f.f_ohg};
-    const uint32_t cnt[4] = {f.n_f_mel, f.n_f_eu, f.n_f_blood, f.n_f_ohg};
-    uint64_t total = 1;
-    for (int k = 0; k < 4; ++k) {
-        require(src[k] && cnt[k] >= 1, "profile fit: each of f_mel, f_eu, f_blood, f_ohg needs at least one value");
-        pl.range[k].assign(src[k], src[k] + cnt[k]);
-        std::sort(pl.range[k].begin(), pl.range[k].end());  // FindParamRange
-        pl.n[k] = cnt[k];
-        total *= cnt[k];
-        require(total <= (1u << 20), "profile fit: more than 2^20 combinations");
-    }
-    require(f.desired_length >= 2 && f.desired_length <= 1024, "profile fit: desired_length outside 2..1024");
-    for (int l = 0; l < 2; ++l)
-        require(f.layer_thickness_nm[l] > 0.f && f.layer_ior[l] > 0.f, "profile fit: layers need thickness and ior > 0");
-    pl.total = (uint32_t)total;
-    float mfp_min = INFINITY, mfp_max = 0.f;
-    for (uint32_t id = 0; with_sigmas && id < pl.total; ++id) {
-        float v[4];
-        pl.params(id, v);
-        skin_fit_mfp_range(v[0], v[1], v[2], v[3], mfp_min, mfp_max);
-    }
-    if (with_sigmas) pl.sigmas = fit_sigma_list(mfp_min, mfp_max);
-    pl.id0 = (uint32_t)std::max(0, f.id_min);
-    pl.id1 = f.id_max < 0 ? pl.total : (uint32_t)std::min<int64_t>(pl.total, f.id_max);
-    if (pl.id1 < pl.id0) pl.id1 = pl.id0;
-    return pl;
+void check_layeredskin(const mpss_layeredskin &m) {
+    require(m.desired_length >= 2 && m.desired_length <= 4096, "desiredlength out of range [2, 4096]");
+    require(m.nmperunit > 0.f, "nmperunit must be positive");
+    require(!m.show_irradiance_points || m.irradiance_point_size > 0.f,
+            "irradiancepointsize must be positive with showirradiancepoints");
 }
 
-// the layers of ids [id0, id1) in millimetres and every channel's own mfp bounds (GaussianFitTask::Run :165-173)
-void fit_layers(const mpss_profilefit &f, const FitPlan &pl, std::vector<LayerParams> &lp, std::vector<float> &mfp_min,
-                std::vector<float> &mfp_max) {
-    const uint32_t n = pl.id1 - pl.id0;
-    lp.resize(n);
-    mfp_min.resize((size_t)n * NB);
-    mfp_max.resize((size_t)n * NB);
-    for (uint32_t i = 0; i < n; ++i) {
-        float v[4];
-        pl.params(pl.id0 + i, v);
-        skin_fit_layer_params(v[0], v[1], v[2], v[3], f.layer_thickness_nm, f.layer_ior, lp[i]);
-        for (int sc = 0; sc < NB; ++sc) {
-            float lo = INFINITY, hi = 0.f;
-            for (int l = 0; l < 2; ++l) {
-                const float mfp = 1.f / (lp[i].mua[l][sc] + lp[i].musp[l][sc]);
-                lo = std::min(lo, mfp);
-                hi = std::max(hi, mfp);
-            }
-            mfp_min[(size_t)i * NB + sc] = lo;
-            mfp_max[(size_t)i * NB + sc] = hi;
+void copy_layer_params(const LayerParams &lp, float *mua, float *musp, float *thickness, float *eta) {
+    memcpy(mua, lp.mua, sizeof(lp.mua));
+    memcpy(musp, lp.musp, sizeof(lp.musp));
+    memcpy(thickness, lp.thickness, sizeof(lp.thickness));
+    memcpy(eta, lp.eta, sizeof(lp.eta));
+}
+
+// nslabs stacks of n layers each, checked and as MpcLayer, with every stack's extent = mfp_range mean free
+// paths (Render, mcprofile.cpp:457-463); `who` prefixes the message
+void mc_reference_layers(const char *who, const mpss_layer *layers, int nslabs, int n, float mfp_range,
+                         std::vector<MpcLayer> &ml, std::vector<double> &extent) {
+    ml.resize((size_t)nslabs * n);
+    extent.resize((size_t)nslabs);
+    for (int s = 0; s < nslabs; ++s) {
+        double mfp_total = 0.;
+        for (int i = 0; i < n; ++i) {
+            const mpss_layer &l = layers[(size_t)s * n + i];
+            if (!(l.musp > 0.f && l.mua >= 0.f && l.thickness > 0.f))
+                throw Error(MPSS_ERR_INVALID, std::string(who) + ": layers need musp > 0, mua >= 0, thickness > 0");
+            ml[(size_t)s * n + i] = MpcLayer{l.mua, l.musp, l.ior, l.thickness};
+            mfp_total += 1. / (double)(l.mua + l.musp);
         }
+        extent[s] = mfp_range * (mfp_total / (double)n);
     }
 }
 
-void fit_rgb_rows(uint32_t n_ids, uint32_t ns, const float *coeffs, float *rgb) {
-    for (uint32_t i = 0; i < n_ids; ++i)
-        for (uint32_t s = 0; s < ns; ++s) {
-            float spec[NB], out[3];
-            for (int sc = 0; sc < NB; ++sc) spec[sc] = coeffs[((size_t)i * NB + sc) * ns + s];
-            spectrum_to_rgb(spec, out);
-            for (int k = 0; k < 3; ++k) rgb[((size_t)i * 3 + k) * ns + s] = out[k];
-        }
-}
-
-void fit_no_candidate(const FitPlan &pl, int64_t profile) {
-    throw Error(MPSS_ERR_INTERNAL, "profile fit: id " + std::to_string(pl.id0 + profile / NB) + " band " +
-                                       std::to_string(profile % NB) +
-                                       " has no candidate window (no sigma within [mfpMin / 2, mfpMax * 2] "
-                                       "with a full window around it)");
-}
 }  // namespace
 
 extern "C" {
@@ -220,10 +169,7 @@ void mpss_layeredskin_defaults(mpss_layeredskin *m) {
 int mpss_add_layeredskin(mpss_ctx *c, const mpss_layeredskin *m, uint32_t *id) {
     return guarded([&] {
         require(c && m && id, "mpss_add_layeredskin: null argument");
-        require(m->desired_length >= 2 && m->desired_length <= 4096, "desiredlength out of range [2, 4096]");
-        require(m->nmperunit > 0.f, "nmperunit must be positive");
-        require(!m->show_irradiance_points || m->irradiance_point_size > 0.f,
-                "irradiancepointsize must be positive with showirradiancepoints");
+        check_layeredskin(*m);
         *id = reinterpret_cast<Context *>(c)->add_layeredskin(*m);
     });
 }
@@ -231,10 +177,7 @@ int mpss_add_layeredskin(mpss_ctx *c, const mpss_layeredskin *m, uint32_t *id) {
 int mpss_update_layeredskin(mpss_ctx *c, uint32_t id, const mpss_layeredskin *m) {
     return guarded([&] {
         require(c && m, "mpss_update_layeredskin: null argument");
-        require(m->desired_length >= 2 && m->desired_length <= 4096, "desiredlength out of range [2, 4096]");
-        require(m->nmperunit > 0.f, "nmperunit must be positive");
-        require(!m->show_irradiance_points || m->irradiance_point_size > 0.f,
-                "irradiancepointsize must be positive with showirradiancepoints");
+        check_layeredskin(*m);
         reinterpret_cast<Context *>(c)->update_layeredskin(id, *m);
     });
 }
@@ -569,16 +512,10 @@ int mpss_mc_reference(const mpss_layer *layers, int n, float mfp_range, int nseg
     return guarded([&] {
         require(layers && refl && trans && tr && tt, "mpss_mc_reference: null argument");
         require(n >= 1 && n <= 8 && nseg >= 1 && nseg <= (1 << 16), "mpss_mc_reference: bad layer or ring count");
-        std::vector<MpcLayer> ml(n);
-        double mfp_total = 0.;
-        for (int i = 0; i < n; ++i) {
-            require(layers[i].musp > 0.f && layers[i].mua >= 0.f && layers[i].thickness > 0.f,
-                    "mpss_mc_reference: layers need musp > 0, mua >= 0, thickness > 0");
-            ml[i] = MpcLayer{layers[i].mua, layers[i].musp, layers[i].ior, layers[i].thickness};
-            mfp_total += 1. / (double)(layers[i].mua + layers[i].musp);  // Render, mcprofile.cpp:457-463
-        }
-        const double extent = mfp_range * (mfp_total / (double)n);
-        mc_reference_profile(ml.data(), n, extent, nseg, lerp != 0, refl, trans, tr, tt);
+        std::vector<MpcLayer> ml;
+        std::vector<double> extent;
+        mc_reference_layers("mpss_mc_reference", layers, 1, n, mfp_range, ml, extent);
+        mc_reference_profile(ml.data(), n, extent[0], nseg, lerp != 0, refl, trans, tr, tt);
     });
 }
 
@@ -607,19 +544,9 @@ int mpss_mc_reference_batch(mpss_ctx *c, const mpss_layer *layers, int nslabs, i
         require(nslabs >= 1 && nslabs <= kMcMaxSlabs, "mpss_mc_reference_batch: 1..65536 slabs supported");
         require(n >= 1 && n <= 8 && nseg >= 1 && nseg <= (1 << 16), "mpss_mc_reference_batch: bad layer or ring count");
         require(desired_length >= 2 && desired_length <= 1024, "mpss_mc_reference_batch: desired length outside 2..1024");
-        std::vector<MpcLayer> ml((size_t)nslabs * n);
-        std::vector<double> extent((size_t)nslabs);
-        for (int s = 0; s < nslabs; ++s) {
-            double mfp_total = 0.;
-            for (int i = 0; i < n; ++i) {
-                const mpss_layer &l = layers[(size_t)s * n + i];
-                require(l.musp > 0.f && l.mua >= 0.f && l.thickness > 0.f,
-                        "mpss_mc_reference_batch: layers need musp > 0, mua >= 0, thickness > 0");
-                ml[(size_t)s * n + i] = MpcLayer{l.mua, l.musp, l.ior, l.thickness};
-                mfp_total += 1. / (double)(l.mua + l.musp);  // Render, mcprofile.cpp:457-463
-            }
-            extent[s] = mfp_range * (mfp_total / (double)n);
-        }
+        std::vector<MpcLayer> ml;
+        std::vector<double> extent;
+        mc_reference_layers("mpss_mc_reference_batch", layers, nslabs, n, mfp_range, ml, extent);
         if (n != 2) {  // the GPU builder combines two layers; other stacks take the host path, slab by slab
             std::vector<double> r((size_t)nseg), t((size_t)nseg);
             for (int s = 0; s < nslabs; ++s) {
@@ -717,10 +644,7 @@ int mpss_host_skin_layers(const mpss_layeredskin *m, float *mua, float *musp, fl
         }
         LayerParams lp;
         skin_layer_params(sp, lp);
-        memcpy(mua, lp.mua, sizeof(lp.mua));
-        memcpy(musp, lp.musp, sizeof(lp.musp));
-        memcpy(thickness, lp.thickness, sizeof(lp.thickness));
-        memcpy(eta, lp.eta, sizeof(lp.eta));
+        copy_layer_params(lp, mua, musp, thickness, eta);
     });
 }
 
@@ -801,9 +725,7 @@ void mpss_profilefit_defaults(mpss_profilefit *f) {
 int mpss_profilefit_params(const mpss_profilefit *f, uint32_t id, float *out) {
     return guarded([&] {
         require(f && out, "mpss_profilefit_params: null argument");
-        const FitPlan pl = make_fit_plan(*f, false);
-        require(id < pl.total, "mpss_profilefit_params: id out of range");
-        pl.params(id, out);
+        profile_fit_id("mpss_profilefit_params", *f, id, out, nullptr);
     });
 }
 
@@ -811,16 +733,10 @@ int mpss_profilefit_layers(const mpss_profilefit *f, uint32_t id, float *mua, fl
                            float *eta) {
     return guarded([&] {
         require(f && mua && musp && thickness && eta, "mpss_profilefit_layers: null argument");
-        const FitPlan pl = make_fit_plan(*f, false);
-        require(id < pl.total, "mpss_profilefit_layers: id out of range");
         float v[4];
-        pl.params(id, v);
         LayerParams lp;
-        skin_fit_layer_params(v[0], v[1], v[2], v[3], f->layer_thickness_nm, f->layer_ior, lp);
-        memcpy(mua, lp.mua, sizeof(lp.mua));
-        memcpy(musp, lp.musp, sizeof(lp.musp));
-        memcpy(thickness, lp.thickness, sizeof(lp.thickness));
-        memcpy(eta, lp.eta, sizeof(lp.eta));
+        profile_fit_id("mpss_profilefit_layers", *f, id, v, &lp);
+        copy_layer_params(lp, mua, musp, thickness, eta);
     });
 }
 
@@ -854,32 +770,11 @@ int mpss_sog_fit(mpss_ctx *c, uint32_t n, uint32_t length, const float *dist_sq,
                 "mpss_sog_fit: null argument");
         require(n >= 1 && length >= 1 && n_sigmas >= 6 && n_sigmas <= 4096,
                 "mpss_sog_fit: needs profiles, samples and 6 .. 4096 sigmas");
-        Context &ctx = *reinterpret_cast<Context *>(c);
-        auto lock = ctx.lock_device();
-        hipStream_t st = (hipStream_t)stream;
-        const size_t cells = (size_t)n * length;
-        DevBuf<float> d_d, d_y, d_coeffs, d_err;
-        DevBuf<int32_t> d_centre;
-        d_d.upload(dist_sq, cells);
-        d_y.upload(data, cells);
-        d_coeffs.alloc((size_t)n * n_sigmas);
-        d_err.alloc(n);
-        d_centre.alloc(n);
-        SogFitWork w;
-        sog_fit_prepare(n, n, (int)n_sigmas, sigmas, mfp_min, mfp_max, w);
-        sog_fit_launch(0, n, length, d_d.ptr, d_y.ptr, d_coeffs.ptr, d_err.ptr, d_centre.ptr, w, st);
-        MPSS_HIP(hipMemcpyAsync(coeffs, d_coeffs.ptr, sizeof(float) * n * n_sigmas, hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipMemcpyAsync(error, d_err.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipMemcpyAsync(centre, d_centre.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
-        if (cand_error)
-            MPSS_HIP(hipMemcpyAsync(cand_error, w.cand_error.ptr, sizeof(float) * n * n_sigmas, hipMemcpyDeviceToHost, st));
-        if (cand_coeffs)
-            MPSS_HIP(hipMemcpyAsync(cand_coeffs, w.cand_coeffs.ptr, sizeof(float) * n * n_sigmas * 6,
-                                    hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipStreamSynchronize(st));
-        for (uint32_t p = 0; p < n; ++p)
-            if (centre[p] < 0)
-                throw Error(MPSS_ERR_INTERNAL, "mpss_sog_fit: profile " + std::to_string(p) + " has no candidate window");
+        auto lock = reinterpret_cast<Context *>(c)->lock_device();
+        const int64_t bad = sog_fit_gpu(n, length, dist_sq, data, (int)n_sigmas, sigmas, mfp_min, mfp_max, coeffs,
+                                        error, centre, cand_error, cand_coeffs, (hipStream_t)stream);
+        if (bad >= 0)
+            throw Error(MPSS_ERR_INTERNAL, "mpss_sog_fit: profile " + std::to_string(bad) + " has no candidate window");
     });
 }
 
@@ -887,85 +782,8 @@ int mpss_profile_fit(mpss_ctx *c, const mpss_profilefit *f, uint32_t *n_sigmas, 
                      float *coeffs, float *error, float *rgb, int32_t *centre, double *stage_ms, void *stream) {
     return guarded([&] {
         require(c && f && n_sigmas && n_ids, "mpss_profile_fit: null argument");
-        const FitPlan pl = make_fit_plan(*f);
-        const uint32_t ns = (uint32_t)pl.sigmas.size(), ni = pl.id1 - pl.id0;
-        *n_sigmas = ns;
-        *n_ids = ni;
-        if (sigmas) memcpy(sigmas, pl.sigmas.data(), sizeof(float) * ns);
-        if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = 0.;
-        if (!coeffs || ni == 0) return;
-        std::vector<LayerParams> lp;
-        std::vector<float> mfp_min, mfp_max;
-        fit_layers(*f, pl, lp, mfp_min, mfp_max);
-        const uint32_t P = ni * NB;
-        // a band without a candidate is known before anything is launched
-        require(ns >= 6, "mpss_profile_fit: the grid's mfp range gives fewer than 6 sigmas");
-        for (uint32_t p = 0; p < P; ++p) {
-            int first, count;
-            sog_candidates((int)ns, pl.sigmas.data(), mfp_min[p], mfp_max[p], first, count);
-            if (!count) fit_no_candidate(pl, p);
-        }
-        Context &ctx = *reinterpret_cast<Context *>(c);
-        auto lock = ctx.lock_device();
-        hipStream_t st = (hipStream_t)stream;
-        const int nent = fit_profile_samples(f->desired_length);
-        // Every allocation and host copy of both stages happens here, before anything is queued: from the
-        // first batch's memset to the copy back, the host only queues work on `st`.
-        FitProfileWork pw;
-        SogFitWork fw;
-        const uint32_t batch = (uint32_t)fit_profiles_prepare(lp.data(), (int)P, f->desired_length,
-                                                              f->max_profiles_per_batch, pw);
-        sog_fit_prepare(P, batch, (int)ns, pl.sigmas.data(), mfp_min.data(), mfp_max.data(), fw);
-        const uint32_t nbatch = (P + batch - 1) / batch;
-        DevBuf<float> d_d, d_y, d_coeffs, d_err;  // d^2 and R of one batch; the results of all P
-        DevBuf<int32_t> d_centre;
-        d_d.alloc((size_t)batch * nent);
-        d_y.alloc((size_t)batch * nent);
-        d_coeffs.alloc((size_t)P * ns);
-        d_err.alloc(P);
-        d_centre.alloc(P);
-        struct Events {
-            std::vector<hipEvent_t> e;
-            ~Events() {
-                for (hipEvent_t x : e)
-                    if (x) (void)hipEventDestroy(x);
-            }
-        } ev;
-        if (stage_ms) {
-            ev.e.assign((size_t)3 * nbatch, nullptr);
-            for (hipEvent_t &x : ev.e) MPSS_HIP(hipEventCreate(&x));
-        }
-        for (uint32_t b = 0; b < nbatch; ++b) {
-            const uint32_t c0 = b * batch, nch = std::min(batch, P - c0);
-            if (stage_ms) MPSS_HIP(hipEventRecord(ev.e[3 * b], st));
-            fit_profiles_launch((int)c0, (int)nch, d_d.ptr, d_y.ptr, pw, st);
-            if (stage_ms) MPSS_HIP(hipEventRecord(ev.e[3 * b + 1], st));
-            // the fit reads the batch's d^2 and R where the profile stage left them: no wait, no copy
-            sog_fit_launch(c0, nch, (uint32_t)nent, d_d.ptr, d_y.ptr, d_coeffs.ptr + (size_t)c0 * ns, d_err.ptr + c0,
-                           d_centre.ptr + c0, fw, st);
-            if (stage_ms) MPSS_HIP(hipEventRecord(ev.e[3 * b + 2], st));
-        }
-        std::vector<float> err(P);
-        std::vector<int32_t> cen(P);
-        MPSS_HIP(hipMemcpyAsync(coeffs, d_coeffs.ptr, sizeof(float) * (size_t)P * ns, hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipMemcpyAsync(err.data(), d_err.ptr, sizeof(float) * P, hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipMemcpyAsync(cen.data(), d_centre.ptr, sizeof(int32_t) * P, hipMemcpyDeviceToHost, st));
-        MPSS_HIP(hipStreamSynchronize(st));
-        if (stage_ms) {
-            for (uint32_t b = 0; b < nbatch; ++b) {
-                float ms = 0.f;
-                MPSS_HIP(hipEventElapsedTime(&ms, ev.e[3 * b], ev.e[3 * b + 1]));
-                stage_ms[0] += ms;
-                MPSS_HIP(hipEventElapsedTime(&ms, ev.e[3 * b + 1], ev.e[3 * b + 2]));
-                stage_ms[1] += ms;
-            }
-            stage_ms[2] = (double)pw.batches;
-        }
-        if (error) memcpy(error, err.data(), sizeof(float) * P);
-        if (centre) memcpy(centre, cen.data(), sizeof(int32_t) * P);
-        for (uint32_t p = 0; p < P; ++p)
-            if (cen[p] < 0) fit_no_candidate(pl, p);  // (every candidate's error was NaN)
-        if (rgb) fit_rgb_rows(ni, ns, coeffs, rgb);
+        profile_fit_gpu(*reinterpret_cast<Context *>(c), *f, n_sigmas, n_ids, sigmas, coeffs, error, rgb, centre,
+                        stage_ms, (hipStream_t)stream);
     });
 }
 
@@ -973,54 +791,7 @@ int mpss_host_profile_fit(const mpss_profilefit *f, uint32_t *n_sigmas, uint32_t
                           float *error, float *rgb, int32_t *centre, uint32_t *length, float *pd, float *py) {
     return guarded([&] {
         require(f && n_sigmas && n_ids, "mpss_host_profile_fit: null argument");
-        const FitPlan pl = make_fit_plan(*f);
-        const uint32_t ns = (uint32_t)pl.sigmas.size(), ni = pl.id1 - pl.id0;
-        *n_sigmas = ns;
-        *n_ids = ni;
-        if (sigmas) memcpy(sigmas, pl.sigmas.data(), sizeof(float) * ns);
-        if (length) *length = 0;
-        if (!coeffs || ni == 0) return;
-        std::vector<LayerParams> lp;
-        std::vector<float> mfp_min, mfp_max;
-        fit_layers(*f, pl, lp, mfp_min, mfp_max);
-        require(ns >= 6, "mpss_host_profile_fit: the grid's mfp range gives fewer than 6 sigmas");
-        const uint32_t P = ni * NB;
-        const size_t L0 = (size_t)fit_profile_samples_host(f->desired_length);
-        std::vector<float> dd((size_t)P * L0), yy((size_t)P * L0);
-        {  // one profile per task over a few host threads (each profile is its own FFTs)
-            std::atomic<uint32_t> next{0};
-            std::atomic<bool> failed{false};
-            std::vector<std::thread> th;
-            const unsigned nt = std::max(1u, std::min({16u, std::thread::hardware_concurrency(), P}));
-            for (unsigned t = 0; t < nt; ++t)
-                th.emplace_back([&] {
-                    std::vector<float> d, y;
-                    for (uint32_t p; (p = next.fetch_add(1)) < P;) {
-                        try {
-                            fit_channel_profile(lp[p / NB], (int)(p % NB), f->desired_length, d, y);
-                            if (d.size() != L0) throw Error(MPSS_ERR_INTERNAL, "profile length");
-                            memcpy(&dd[(size_t)p * L0], d.data(), sizeof(float) * L0);
-                            memcpy(&yy[(size_t)p * L0], y.data(), sizeof(float) * L0);
-                        } catch (...) {
-                            failed = true;
-                        }
-                    }
-                });
-            for (auto &x : th) x.join();
-            if (failed) throw Error(MPSS_ERR_INTERNAL, "mpss_host_profile_fit: a host profile build failed");
-        }
-        const uint32_t L = (uint32_t)(dd.size() / P);
-        if (length) *length = L;
-        if (pd) memcpy(pd, dd.data(), sizeof(float) * dd.size());
-        if (py) memcpy(py, yy.data(), sizeof(float) * yy.size());
-        std::vector<float> err(P);
-        std::vector<int32_t> cen(P);
-        const int64_t bad = sog_fit_host(P, L, dd.data(), yy.data(), (int)ns, pl.sigmas.data(), mfp_min.data(),
-                                         mfp_max.data(), coeffs, err.data(), cen.data(), nullptr, nullptr, nullptr);
-        if (error) memcpy(error, err.data(), sizeof(float) * P);
-        if (centre) memcpy(centre, cen.data(), sizeof(int32_t) * P);
-        if (bad >= 0) fit_no_candidate(pl, bad);
-        if (rgb) fit_rgb_rows(ni, ns, coeffs, rgb);
+        profile_fit_host(*f, n_sigmas, n_ids, sigmas, coeffs, error, rgb, centre, length, pd, py);
     });
 }
 

@@ -28,20 +28,21 @@
 
 namespace mpss {
 
-namespace {
-
-constexpr float kPiMPC = 3.141592654f;  // numutil.h:45
-constexpr int kPairs = 11;              // dipole pairs -5..5 (DipoleCalculator)
+constexpr int kPairs = 11;  // dipole pairs -5..5 (DipoleCalculator)
 
 struct DipoleP {
     float d, zpos, zneg, str, alphap;
 };
-struct ChanSetup {
+struct ChanSetup {  // (named in material.h: GridWork holds an array of these)
     float s2;          // step^2 (float)
     double nf;         // step^2 as double
     double lerp[2];    // lerp-on-thin-slab weight per layer
     DipoleP dip[2][kPairs];
 };
+
+namespace {
+
+constexpr float kPiMPC = 3.141592654f;  // numutil.h:45
 
 float fresnel_diffuse_h(float eta) {  // DipoleCalculator.cpp:38-46
     if (eta >= 1.f) return -1.4399f / (eta * eta) + 0.7099f / eta + 0.6681f + 0.0636f * eta;
@@ -362,99 +363,142 @@ unsigned round_up_pow2_u(unsigned v) {
     return v + 1;
 }
 
+// ---- the grid pipeline: one plan, one workspace, one launch sequence for the three drivers below
+
+// Sizes for n_channels channels at desired_length; the batch is what grid_budget_bytes of grids hold, the
+// caller's cap (max_batch > 0) and the launch grids' limit (grid.y = 4 nch <= 65535) allow.
+GridPlan make_grid_plan(int desired_length, int n_channels, int max_batch, size_t grid_budget_bytes) {
+    if (n_channels < 1) throw Error(-1, "multipole grids: no channels");
+    GridPlan p;
+    p.length = (int)round_up_pow2_u((unsigned)desired_length);
+    p.N = 2 * p.length;
+    p.M = 2 * p.N;
+    p.logM = 0;
+    while ((1 << p.logM) < p.M) ++p.logM;
+    if (desired_length < 2 || p.M > 4096) throw Error(-1, "multipole grids: desired length outside 2..1024");
+    p.ext = p.length - 1;
+    p.nent = (int)unique_list((unsigned)p.ext).nsq.size();
+    p.cols = std::max(1, std::min(4, 131072 / (p.M * (int)sizeof(double2))));
+    const size_t grid_bytes = (size_t)p.M * p.M * sizeof(double2);
+    size_t batch = std::max<size_t>(1, grid_budget_bytes / (4 * grid_bytes));
+    batch = std::min<size_t>(batch, 16383);
+    if (max_batch > 0) batch = std::min<size_t>(batch, (size_t)max_batch);
+    p.batch = (int)std::min<size_t>(batch, (size_t)n_channels);
+    return p;
+}
+
+// twiddles exp(-2 pi i k / M)
+std::vector<double2> make_twiddles(int M) {
+    std::vector<double2> tw(M / 2);
+    for (int k = 0; k < M / 2; ++k) {
+        const double ph = -2.0 * M_PI * (double)k / (double)M;
+        tw[k] = make_double2(cos(ph), sin(ph));
+    }
+    return tw;
+}
+
+// Every allocation and every (blocking) upload of the pipeline for the channels cs / steps, and the kernels'
+// dynamic-LDS limits, which have to be raised before the first launch at this M: at M = 4096 the rows
+// kernel needs 64 KB and the columns kernel 128 KB.
+void grid_prepare(const GridPlan &p, const std::vector<ChanSetup> &cs, const std::vector<float> &steps, bool with_t,
+                  GridWork &w) {
+    const UniqueList &ul = unique_list((unsigned)p.ext);
+    const std::vector<double2> tw = make_twiddles(p.M);
+    w.plan = p;
+    w.n = (int)cs.size();
+    w.batches = 0;
+    w.tw.upload(tw.data(), tw.size());
+    w.setup.upload(cs.data(), cs.size());
+    w.ij.upload(ul.ij.data(), ul.ij.size());
+    w.nsq.upload(ul.nsq.data(), ul.nsq.size());
+    w.step.upload(steps.data(), steps.size());
+    w.d.alloc((size_t)p.batch * p.nent);
+    w.r.alloc((size_t)p.batch * p.nent);
+    if (with_t) w.t.alloc((size_t)p.batch * p.nent);
+    w.grids.alloc((size_t)p.batch * 4 * p.M * p.M);
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 p.cols * p.M * (int)sizeof(double2)));
+    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 p.M * (int)sizeof(double2)));
+}
+
+// One batch, channels c0 .. c0 + nch - 1 (nch <= the plan's batch): their time-domain R12 is left in slot 0
+// of w.grids (T12 in slot 1 when with_t) and its unique-d^2 samples in w.d / w.r (w.t) [nch][nent].
+// A memset and kernels on `stream` only: nothing is allocated, copied from the host or waited for.
+void grid_launch(GridWork &w, int c0, int nch, bool with_t, hipStream_t stream) {
+    const GridPlan &p = w.plan;
+    if (nch < 1 || nch > p.batch || c0 < 0 || c0 + nch > w.n || (with_t && !w.t.ptr))
+        throw Error(-1, "multipole grids: range outside the prepared work");
+    const int M = p.M, logM = p.logM, cols = p.cols, nent = p.nent;
+    const size_t mm = (size_t)M * M, chan_stride = 4 * mm, row_lds = M * sizeof(double2), col_lds = cols * row_lds;
+    double2 *g = w.grids.ptr;
+    MPSS_HIP(hipMemsetAsync(g, 0, (size_t)nch * chan_stride * sizeof(double2), stream));
+    const int64_t cells = (int64_t)(p.ext + 1) * (p.ext + 1) * 2 * nch;
+    hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, w.setup.ptr + c0,
+                       nch, p.ext, M, g);
+    // forward 2-D transforms of all 4 grids
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 4), (unsigned)nch), dim3(256), row_lds, stream, g, M, logM,
+                       w.tw.ptr, 0, chan_stride);
+    hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256), col_lds, stream, g,
+                       M, logM, cols, w.tw.ptr, 0, mm);
+    const int64_t freq = (int64_t)mm * nch;
+    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, g, nch, M,
+                       with_t ? 1 : 0);
+    // inverse transforms of every channel's R12 (slot 0) and T12 (slot 1, with_t), folded over the channels:
+    // the two slots are adjacent, so one rows launch covers both; the columns go slot by slot
+    const int slots = with_t ? 2 : 1;
+    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * slots), (unsigned)nch), dim3(256), row_lds, stream, g, M,
+                       logM, w.tw.ptr, 1, chan_stride);
+    for (int slot = 0; slot < slots; ++slot)
+        hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)nch), dim3(256), col_lds, stream,
+                           g + slot * mm, M, logM, cols, w.tw.ptr, 1, chan_stride);
+    // the readout takes a channel's grid at grids + ch * 4 M^2: offset by one grid it reads T12
+    float *const out[2] = {w.r.ptr, w.t.ptr};
+    const unsigned rb = (unsigned)(((int64_t)nent * nch + 255) / 256);
+    for (int slot = 0; slot < slots; ++slot)
+        hipLaunchKernelGGL(readout_kernel, dim3(rb), dim3(256), 0, stream, g + slot * mm, nch, M, w.ij.ptr, w.nsq.ptr,
+                           nent, w.step.ptr + c0, w.d.ptr, out[slot]);
+    MPSS_HIP(hipGetLastError());
+    ++w.batches;
+}
+
 }  // namespace
 
 void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin, ProfileTables &out,
                        hipStream_t stream, int distinct) {
     if (distinct < 1 || distinct > NB) throw Error(-1, "build_profile_gpu: distinct channels out of range");
     const int NC = distinct;  // channels built; channel c >= NC copies channel c % NC
-    const int length = (int)round_up_pow2_u((unsigned)desired_length);
-    const int N = 2 * length, M = 2 * N;
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
-    if (M > 4096) throw Error(-1, "build_profile_gpu: desiredlength above 1024 not supported on the GPU path");
-    const int ext = length - 1;
-    // per-channel setup (channel_profile / layer_grid, material.cpp)
+    // 3 GB of grids at most, so that a render context's peak memory stays where it was
+    const GridPlan p = make_grid_plan(desired_length, NC, 0, (size_t)3 << 30);
+    const int nent = p.nent, tl = 2 * nent;
     std::vector<ChanSetup> cs(NC);
     std::vector<float> steps(NC);
     for (int sc = 0; sc < NC; ++sc) steps[sc] = chan_setup(lp, sc, desired_length, lerp_thin, cs[sc]);
-    const UniqueList &ul = unique_list((unsigned)ext);
-    const int nent = (int)ul.nsq.size();
-    const int tl = 2 * nent;
-    // twiddles exp(-2 pi i k / M)
-    std::vector<double2> tw(M / 2);
-    for (int k = 0; k < M / 2; ++k) {
-        const double ph = -2.0 * M_PI * (double)k / (double)M;
-        tw[k] = make_double2(cos(ph), sin(ph));
-    }
-    DevBuf<double2> d_tw;
-    d_tw.upload(tw.data(), tw.size());
-    DevBuf<ChanSetup> d_cs;
-    d_cs.upload(cs.data(), cs.size());
-    DevBuf<int2> d_ij;
-    d_ij.upload(ul.ij.data(), ul.ij.size());
-    DevBuf<uint32_t> d_nsq;
-    d_nsq.upload(ul.nsq.data(), ul.nsq.size());
-    DevBuf<float> d_step, d_d, d_r, d_table;
-    d_step.upload(steps.data(), steps.size());
-    d_d.alloc((size_t)NC * nent);
-    d_r.alloc((size_t)NC * nent);
+    GridWork w;
+    grid_prepare(p, cs, steps, false, w);
+    DevBuf<float> d_table;
     d_table.alloc((size_t)NC * tl);
     DevBuf<double> d_tot;
     d_tot.alloc(NC);
-    // channels in batches that keep the 4 complex grids per channel within ~3 GB
-    const size_t grid_bytes = (size_t)M * M * sizeof(double2);
-    const int batch = (int)std::max<size_t>(1, std::min<size_t>(NC, ((size_t)3 << 30) / (4 * grid_bytes)));
-    DevBuf<double2> grids;
-    grids.alloc((size_t)batch * 4 * M * M);
-    const int cols = std::max(1, std::min(4, 131072 / (M * (int)sizeof(double2))));
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 cols * M * (int)sizeof(double2)));
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 M * (int)sizeof(double2)));
-    for (int c0 = 0; c0 < NC; c0 += batch) {
-        const int nch = std::min(batch, NC - c0);
-        MPSS_HIP(hipMemsetAsync(grids.ptr, 0, (size_t)nch * 4 * grid_bytes, stream));
-        const int64_t cells = (int64_t)(ext + 1) * (ext + 1) * 2 * nch;
-        hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream,
-                           d_cs.ptr + c0, nch, ext, M, grids.ptr);
-        // forward 2-D transforms of all 4 grids
-        hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * nch * 4)), dim3(256), M * sizeof(double2), stream,
-                           grids.ptr, M, logM, d_tw.ptr, 0, (size_t)0);
-        hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
-                           (size_t)cols * M * sizeof(double2), stream, grids.ptr, M, logM, cols, d_tw.ptr, 0,
-                           (size_t)M * M);
-        const int64_t freq = (int64_t)M * M * nch;
-        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, grids.ptr, nch,
-                           M, 0);
-        // inverse transform of R12 (slot 0 of each channel): rows of the slot-0 matrices only
-        for (int ch = 0; ch < nch; ++ch) {
-            double2 *g = grids.ptr + (size_t)ch * 4 * M * M;
-            hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)M), dim3(256), M * sizeof(double2), stream, g, M, logM,
-                               d_tw.ptr, 1, (size_t)0);
-            hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), 1u), dim3(256),
-                               (size_t)cols * M * sizeof(double2), stream, g, M, logM, cols, d_tw.ptr, 1, (size_t)0);
-        }
-        hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((nent * nch + 255) / 256)), dim3(256), 0, stream, grids.ptr,
-                           nch, M, d_ij.ptr, d_nsq.ptr, nent, d_step.ptr + c0, d_d.ptr + (size_t)c0 * nent,
-                           d_r.ptr + (size_t)c0 * nent);
-        hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, grids.ptr, M, N, 0,
+    std::vector<float> dlast(NC);
+    for (int c0 = 0; c0 < NC; c0 += p.batch) {
+        const int nch = std::min(p.batch, NC - c0);
+        grid_launch(w, c0, nch, false, stream);
+        hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, w.grids.ptr, p.M, p.N, 0,
                            d_tot.ptr + c0, 1);
+        hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((tl * nch + 255) / 256)), dim3(256), 0, stream, w.d.ptr,
+                           w.r.ptr, nent, nch, tl, d_table.ptr + (size_t)c0 * tl);
         MPSS_HIP(hipGetLastError());
+        for (int c = 0; c < nch; ++c)  // the channel's extent, before the next batch overwrites w.d
+            MPSS_HIP(hipMemcpyAsync(&dlast[c0 + c], w.d.ptr + (size_t)c * nent + nent - 1, sizeof(float),
+                                    hipMemcpyDeviceToHost, stream));
     }
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)((tl * NC + 255) / 256)), dim3(256), 0, stream, d_d.ptr,
-                       d_r.ptr, nent, NC, tl, d_table.ptr);
-    MPSS_HIP(hipGetLastError());
     out.length = tl;
     out.table.resize((size_t)NB * tl);
-    std::vector<float> dlast(NC);
     std::vector<double> tot(NC);
     MPSS_HIP(hipMemcpyAsync(out.table.data(), d_table.ptr, sizeof(float) * (size_t)NC * tl, hipMemcpyDeviceToHost,
                             stream));
     MPSS_HIP(hipMemcpyAsync(tot.data(), d_tot.ptr, sizeof(double) * NC, hipMemcpyDeviceToHost, stream));
-    for (int c = 0; c < NC; ++c)
-        MPSS_HIP(hipMemcpyAsync(&dlast[c], d_d.ptr + (size_t)c * nent + nent - 1, sizeof(float), hipMemcpyDeviceToHost,
-                                stream));
     MPSS_HIP(hipStreamSynchronize(stream));
     for (int c = NC; c < NB; ++c)
         memcpy(&out.table[(size_t)c * tl], &out.table[(size_t)(c % NC) * tl], sizeof(float) * tl);
@@ -467,188 +511,56 @@ void build_profile_gpu(const LayerParams &lp, int desired_length, bool lerp_thin
     }
 }
 
-int fit_profile_samples(int desired_length) {
-    return (int)unique_list(round_up_pow2_u((unsigned)desired_length) - 1).nsq.size();
-}
-
-// GaussianFitTask::Run's profiles (profilefit.cpp:158-192) for n channels: the stages of build_profile_gpu
-// over batches of channels, the inverse transform of a batch's slot-0 grids folded into one rows and one
-// columns launch, the fit's resampling last.
-// prepare: every allocation and host copy (blocking), for all n channels; returns the batch size.
-int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, FitProfileWork &w) {
-    if (n < 1) throw Error(-1, "fit_profiles_prepare: no channels");
-    const int length = (int)round_up_pow2_u((unsigned)desired_length);
-    const int N = 2 * length, M = 2 * N;
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
-    if (desired_length < 2 || M > 4096) throw Error(-1, "fit_profiles_prepare: desired length outside 2..1024");
-    const int ext = length - 1;
+// GaussianFitTask::Run's profiles (profilefit.cpp:158-192) for n channels: the grid pipeline with the thin-slab
+// lerp on, then the fit's resampling.
+int fit_profiles_prepare(const LayerParams *lp, int n, int desired_length, int max_batch, GridWork &w) {
+    const GridPlan p = make_grid_plan(desired_length, n, max_batch, (size_t)8 << 30);
     std::vector<ChanSetup> cs((size_t)n);
     std::vector<float> steps((size_t)n);
     for (int i = 0; i < n; ++i) steps[i] = chan_setup(lp[i / NB], i % NB, desired_length, true, cs[i]);
-    const UniqueList &ul = unique_list((unsigned)ext);
-    const int nent = (int)ul.nsq.size();
-    std::vector<double2> tw(M / 2);
-    for (int k = 0; k < M / 2; ++k) {
-        const double ph = -2.0 * M_PI * (double)k / (double)M;
-        tw[k] = make_double2(cos(ph), sin(ph));
-    }
-    // batch: the workspace limit, the caller's cap, and the launch grids' limits (grid.y = 4 nch <= 65535)
-    const size_t grid_bytes = (size_t)M * M * sizeof(double2);
-    size_t batch = std::max<size_t>(1, ((size_t)8 << 30) / (4 * grid_bytes));
-    batch = std::min<size_t>(batch, 16383);
-    if (max_batch > 0) batch = std::min<size_t>(batch, (size_t)max_batch);
-    batch = std::min<size_t>(batch, (size_t)n);
-    w.tw.upload(tw.data(), tw.size());
-    w.setup.upload(reinterpret_cast<const unsigned char *>(cs.data()), cs.size() * sizeof(ChanSetup));
-    w.ij.upload(ul.ij.data(), ul.ij.size());
-    w.nsq.upload(ul.nsq.data(), ul.nsq.size());
-    w.step.upload(steps.data(), steps.size());
-    w.d.alloc(batch * nent);
-    w.r.alloc(batch * nent);
-    w.grids.alloc(batch * 4 * M * M);
-    w.n = n;
-    w.batch = (int)batch;
-    w.M = M;
-    w.logM = logM;
-    w.ext = ext;
-    w.nent = nent;
-    w.cols = std::max(1, std::min(4, 131072 / (M * (int)sizeof(double2))));
-    w.batches = 0;
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 w.cols * M * (int)sizeof(double2)));
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 M * (int)sizeof(double2)));
-    return w.batch;
+    grid_prepare(p, cs, steps, false, w);
+    return p.batch;
 }
 
-// one batch: channels c0 .. c0 + nch - 1 (nch <= the prepared batch size) into dsq_dev / refl_dev [nch][nent].
-// Memset and kernels on `stream` only: nothing is allocated, copied from the host or waited for.
-void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, FitProfileWork &w, hipStream_t stream) {
-    if (nch < 1 || nch > w.batch || c0 < 0 || c0 + nch > w.n)
-        throw Error(-1, "fit_profiles_launch: range outside the prepared work");
-    const int M = w.M, logM = w.logM, ext = w.ext, nent = w.nent, cols = w.cols;
-    const size_t grid_bytes = (size_t)M * M * sizeof(double2);
-    const ChanSetup *d_cs = reinterpret_cast<const ChanSetup *>(w.setup.ptr);
-    const size_t chan_stride = (size_t)4 * M * M;
-    MPSS_HIP(hipMemsetAsync(w.grids.ptr, 0, (size_t)nch * 4 * grid_bytes, stream));
-    const int64_t cells = (int64_t)(ext + 1) * (ext + 1) * 2 * nch;
-    hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, d_cs + c0, nch, ext,
-                       M, w.grids.ptr);
-    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 4), (unsigned)nch), dim3(256), M * sizeof(double2), stream,
-                       w.grids.ptr, M, logM, w.tw.ptr, 0, chan_stride);
-    hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
-                       (size_t)cols * M * sizeof(double2), stream, w.grids.ptr, M, logM, cols, w.tw.ptr, 0,
-                       (size_t)M * M);
-    const int64_t freq = (int64_t)M * M * nch;
-    hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, w.grids.ptr, nch, M,
-                       0);
-    // inverse transform of every channel's R12 (slot 0): one rows launch, one columns launch
-    hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)M, (unsigned)nch), dim3(256), M * sizeof(double2), stream,
-                       w.grids.ptr, M, logM, w.tw.ptr, 1, chan_stride);
-    hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)nch), dim3(256),
-                       (size_t)cols * M * sizeof(double2), stream, w.grids.ptr, M, logM, cols, w.tw.ptr, 1, chan_stride);
-    hipLaunchKernelGGL(readout_kernel, dim3((unsigned)((nent * nch + 255) / 256)), dim3(256), 0, stream, w.grids.ptr,
-                       nch, M, w.ij.ptr, w.nsq.ptr, nent, w.step.ptr + c0, w.d.ptr, w.r.ptr);
+void fit_profiles_launch(int c0, int nch, float *dsq_dev, float *refl_dev, GridWork &w, hipStream_t stream) {
+    grid_launch(w, c0, nch, false, stream);
+    const int nent = w.plan.nent;
     hipLaunchKernelGGL(resample_fit_kernel, dim3((unsigned)(((int64_t)nent * nch + 255) / 256)), dim3(256), 0, stream,
                        w.d.ptr, w.r.ptr, nent, nch, dsq_dev, refl_dev);
     MPSS_HIP(hipGetLastError());
-    ++w.batches;
 }
 
 // MultipoleReferenceTask::Run (renderers/mcprofile.cpp:381-425) for nslabs two-layer stacks: what
-// mc_reference_profile (material.cpp) computes on the host, with the stages of fit_profiles_launch over
-// batches of slabs. Beyond the fit's profile: the step is (float)(extent * 1.01 / desired_length), the
-// combine writes T12 beside R12, both come back to the time domain, both are read out and Kahan-summed,
-// and the profile is read at the ring centres. A slab's grids are its own, so its result does not depend
-// on the batch size. Every allocation and upload happens before the first launch; one wait at the end.
+// mc_reference_profile (material.cpp) computes on the host. Beyond the fit's profile: the step is
+// (float)(extent * 1.01 / desired_length), the combine writes T12 beside R12, both come back to the time
+// domain, both are read out and Kahan-summed, and the profile is read at the ring centres. A slab's grids
+// are its own, so its result does not depend on the batch size. One wait at the end.
 void mc_reference_batch_gpu(const MpcLayer *layers, int nslabs, const double *extent, int nsegments,
                             int desired_length, bool lerp_thin, int max_batch, double *refl, double *trans,
                             double *total_r, double *total_t, hipStream_t stream) {
-    if (nslabs < 1) throw Error(-1, "mc_reference_batch: no slabs");
-    const int length = (int)round_up_pow2_u((unsigned)desired_length);
-    const int N = 2 * length, M = 2 * N;
-    int logM = 0;
-    while ((1 << logM) < M) ++logM;
-    if (desired_length < 2 || M > 4096) throw Error(-1, "mc_reference_batch: desired length outside 2..1024");
-    const int ext = length - 1;
+    // 8 GB of grids at most: 1 GiB per slab at M = 4096
+    const GridPlan p = make_grid_plan(desired_length, nslabs, max_batch, (size_t)8 << 30);
     std::vector<ChanSetup> cs((size_t)nslabs);
     std::vector<float> steps((size_t)nslabs);
     for (int s = 0; s < nslabs; ++s) {
         steps[s] = (float)(extent[s] * 1.01 / desired_length);
         two_layer_setup(layers + 2 * (size_t)s, steps[s], lerp_thin, cs[s]);
     }
-    const UniqueList &ul = unique_list((unsigned)ext);
-    const int nent = (int)ul.nsq.size();
-    std::vector<double2> tw(M / 2);
-    for (int k = 0; k < M / 2; ++k) {
-        const double ph = -2.0 * M_PI * (double)k / (double)M;
-        tw[k] = make_double2(cos(ph), sin(ph));
-    }
-    // batch: the workspace limit (8 GB of grids; 1 GiB per slab at M = 4096), the caller's cap, and the
-    // launch grids' limits (grid.y = 4 nch <= 65535)
-    const size_t mm = (size_t)M * M, grid_bytes = mm * sizeof(double2);
-    size_t batch = std::max<size_t>(1, ((size_t)8 << 30) / (4 * grid_bytes));
-    batch = std::min<size_t>(batch, 16383);
-    if (max_batch > 0) batch = std::min<size_t>(batch, (size_t)max_batch);
-    batch = std::min<size_t>(batch, (size_t)nslabs);
-    DevBuf<double2> d_tw, grids;
-    DevBuf<ChanSetup> d_cs;
-    DevBuf<int2> d_ij;
-    DevBuf<uint32_t> d_nsq;
-    DevBuf<float> d_step, d_d, d_r, d_t;
+    GridWork w;
+    grid_prepare(p, cs, steps, true, w);
     DevBuf<double> d_ext, d_out;  // d_out: rings R [nslabs][nseg], rings T, then totals [nslabs][2]
-    d_tw.upload(tw.data(), tw.size());
-    d_cs.upload(cs.data(), cs.size());
-    d_ij.upload(ul.ij.data(), ul.ij.size());
-    d_nsq.upload(ul.nsq.data(), ul.nsq.size());
-    d_step.upload(steps.data(), steps.size());
     d_ext.upload(extent, (size_t)nslabs);
-    d_d.alloc(batch * nent);
-    d_r.alloc(batch * nent);
-    d_t.alloc(batch * nent);
-    grids.alloc(batch * 4 * mm);
     const size_t nring = (size_t)nslabs * nsegments;
     d_out.alloc(2 * nring + 2 * (size_t)nslabs);
     double *o_r = d_out.ptr, *o_t = o_r + nring, *o_tot = o_t + nring;
-    const int cols = std::max(1, std::min(4, 131072 / (M * (int)sizeof(double2))));
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_cols_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 cols * M * (int)sizeof(double2)));
-    MPSS_HIP(hipFuncSetAttribute((const void *)fft_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 M * (int)sizeof(double2)));
-    const size_t chan_stride = 4 * mm;
-    for (int c0 = 0; c0 < nslabs; c0 += (int)batch) {
-        const int nch = std::min((int)batch, nslabs - c0);
-        MPSS_HIP(hipMemsetAsync(grids.ptr, 0, (size_t)nch * 4 * grid_bytes, stream));
-        const int64_t cells = (int64_t)(ext + 1) * (ext + 1) * 2 * nch;
-        hipLaunchKernelGGL(grid_fill_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, stream, d_cs.ptr + c0,
-                           nch, ext, M, grids.ptr);
-        hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 4), (unsigned)nch), dim3(256), M * sizeof(double2),
-                           stream, grids.ptr, M, logM, d_tw.ptr, 0, chan_stride);
-        hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)(nch * 4)), dim3(256),
-                           (size_t)cols * M * sizeof(double2), stream, grids.ptr, M, logM, cols, d_tw.ptr, 0, mm);
-        const int64_t freq = (int64_t)mm * nch;
-        hipLaunchKernelGGL(combine_kernel, dim3((unsigned)((freq + 255) / 256)), dim3(256), 0, stream, grids.ptr, nch, M,
-                           1);
-        // inverse transforms of R12 (slot 0) and T12 (slot 1): the two slots are adjacent, so one rows launch
-        // covers both; the columns go slot by slot
-        hipLaunchKernelGGL(fft_rows_kernel, dim3((unsigned)(M * 2), (unsigned)nch), dim3(256), M * sizeof(double2),
-                           stream, grids.ptr, M, logM, d_tw.ptr, 1, chan_stride);
+    for (int c0 = 0; c0 < nslabs; c0 += p.batch) {
+        const int nch = std::min(p.batch, nslabs - c0);
+        grid_launch(w, c0, nch, true, stream);
         for (int slot = 0; slot < 2; ++slot)
-            hipLaunchKernelGGL(fft_cols_kernel, dim3((unsigned)(M / cols), (unsigned)nch), dim3(256),
-                               (size_t)cols * M * sizeof(double2), stream, grids.ptr + slot * mm, M, logM, cols, d_tw.ptr,
-                               1, chan_stride);
-        // the readout takes a channel's grid at grids + ch * 4 M^2: offset by one grid it reads T12
-        const unsigned rb = (unsigned)(((int64_t)nent * nch + 255) / 256);
-        hipLaunchKernelGGL(readout_kernel, dim3(rb), dim3(256), 0, stream, grids.ptr, nch, M, d_ij.ptr, d_nsq.ptr, nent,
-                           d_step.ptr + c0, d_d.ptr, d_r.ptr);
-        hipLaunchKernelGGL(readout_kernel, dim3(rb), dim3(256), 0, stream, grids.ptr + mm, nch, M, d_ij.ptr, d_nsq.ptr,
-                           nent, d_step.ptr + c0, d_d.ptr, d_t.ptr);
-        for (int slot = 0; slot < 2; ++slot)
-            hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, grids.ptr, M, N, slot,
+            hipLaunchKernelGGL(total_kernel, dim3((unsigned)nch), dim3(256), 0, stream, w.grids.ptr, p.M, p.N, slot,
                                o_tot + 2 * (size_t)c0 + slot, 2);
         hipLaunchKernelGGL(ring_resample_kernel, dim3((unsigned)(((int64_t)nsegments * nch + 255) / 256)), dim3(256), 0,
-                           stream, d_d.ptr, d_r.ptr, d_t.ptr, nent, nch, d_ext.ptr + c0, nsegments,
+                           stream, w.d.ptr, w.r.ptr, w.t.ptr, p.nent, nch, d_ext.ptr + c0, nsegments,
                            o_r + (size_t)c0 * nsegments, o_t + (size_t)c0 * nsegments);
         MPSS_HIP(hipGetLastError());
     }
@@ -664,3 +576,4 @@ void mc_reference_batch_gpu(const MpcLayer *layers, int nslabs, const double *ex
 }
 
 }  // namespace mpss
+

@@ -24,5 +24,10 @@ void sog_fit_prepare(uint32_t n, uint32_t capacity, int n_sigmas, const float *s
 // w.cand_coeffs [count][n_sigmas][6] until the next launch.
 void sog_fit_launch(uint32_t p0, uint32_t count, uint32_t length, const float *dist_sq_dev, const float *data_dev,
                     float *coeffs_dev, float *error_dev, int32_t *centre_dev, SogFitWork &w, hipStream_t stream);
+// The whole fit of n host-resident profiles, arguments and result as sog_fit_host's (profile_fit.h): upload,
+// prepare, one launch, copy back, wait.
+int64_t sog_fit_gpu(uint32_t n, uint32_t length, const float *dist_sq, const float *data, int n_sigmas,
+                    const float *sigmas, const float *mfp_min, const float *mfp_max, float *coeffs, float *error,
+                    int32_t *centre, float *cand_error, float *cand_coeffs, hipStream_t stream);
 
 }  // namespace mpss

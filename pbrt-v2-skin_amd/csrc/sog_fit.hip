@@ -173,4 +173,31 @@ void sog_fit_launch(uint32_t p0, uint32_t count, uint32_t length, const float *d
     MPSS_HIP(hipGetLastError());
 }
 
+int64_t sog_fit_gpu(uint32_t n, uint32_t length, const float *dist_sq, const float *data, int n_sigmas,
+                    const float *sigmas, const float *mfp_min, const float *mfp_max, float *coeffs, float *error,
+                    int32_t *centre, float *cand_error, float *cand_coeffs, hipStream_t st) {
+    const size_t cells = (size_t)n * length, ns = (size_t)n_sigmas;
+    DevBuf<float> d_d, d_y, d_coeffs, d_err;
+    DevBuf<int32_t> d_centre;
+    d_d.upload(dist_sq, cells);
+    d_y.upload(data, cells);
+    d_coeffs.alloc(n * ns);
+    d_err.alloc(n);
+    d_centre.alloc(n);
+    SogFitWork w;
+    sog_fit_prepare(n, n, n_sigmas, sigmas, mfp_min, mfp_max, w);
+    sog_fit_launch(0, n, length, d_d.ptr, d_y.ptr, d_coeffs.ptr, d_err.ptr, d_centre.ptr, w, st);
+    MPSS_HIP(hipMemcpyAsync(coeffs, d_coeffs.ptr, sizeof(float) * n * ns, hipMemcpyDeviceToHost, st));
+    MPSS_HIP(hipMemcpyAsync(error, d_err.ptr, sizeof(float) * n, hipMemcpyDeviceToHost, st));
+    MPSS_HIP(hipMemcpyAsync(centre, d_centre.ptr, sizeof(int32_t) * n, hipMemcpyDeviceToHost, st));
+    if (cand_error)
+        MPSS_HIP(hipMemcpyAsync(cand_error, w.cand_error.ptr, sizeof(float) * n * ns, hipMemcpyDeviceToHost, st));
+    if (cand_coeffs)
+        MPSS_HIP(hipMemcpyAsync(cand_coeffs, w.cand_coeffs.ptr, sizeof(float) * n * ns * 6, hipMemcpyDeviceToHost, st));
+    MPSS_HIP(hipStreamSynchronize(st));
+    for (uint32_t p = 0; p < n; ++p)
+        if (centre[p] < 0) return p;
+    return -1;
+}
+
 }  // namespace mpss
