@@ -151,12 +151,7 @@ void Context::mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, 
     }
     int *perm = nullptr;
     if (ws) {
-        const int64_t need = ((int64_t)q + 1023) / 1024 * 1024;
-        if (ws->perm_n < need) {
-            if (ws->pending) MPSS_HIP(hipEventSynchronize(ws->done));
-            ws->perm.alloc((size_t)need);
-            ws->perm_n = need;
-        }
+        ws->reserve(ws->perm, (size_t)(((int64_t)q + 1023) / 1024 * 1024));
         perm = ws->perm.ptr;
         if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));
     }

@@ -15,6 +15,7 @@
 #include "replay.h"
 #include "scene.h"
 #include "texture_build.h"
+#include "tile_plan.h"
 
 namespace mpss {
 
@@ -72,12 +73,11 @@ std::unique_ptr<ImageTexture> build_imagemap(const mpss_imagemap &m);
 // Per-sample buffers (flags, slot, and the hit records primary_kernel writes: ha, hb, hs) are sized
 // for the batch's camera samples; everything after the hit compaction (Mo() queries and results,
 // direct-light terms, XYZ) for the batch's actual hit count, which render_tiles reads back once per
-// batch.
+// batch. Every buffer records its own size (DevBuf::n) and only grows, through reserve().
 struct RenderWorkspace {
     DevBuf<uint32_t> flags, hs, spill;
     DevBuf<int32_t> slot;
     DevBuf<int> count, work, perm;  // perm: the sharded gather's sorted query ids
-    int64_t perm_n = 0;
     DevBuf<float4> q, mo, ha, hb, xyz, alb, frame, st;
     DevBuf<unsigned char> terms;
     DevBuf<float> ld;
@@ -87,10 +87,17 @@ struct RenderWorkspace {
     DevBuf<uint32_t> rp_mt;
     DevBuf<int> rp_pix, rp_mti;
     uint64_t rp_key[3] = {~0ull, 0, 0};
-    int64_t n = 0, rec_n = 0, hits = 0, tex_hits = 0, terms_n = 0, st_n = 0, px = 0;
     hipEvent_t done = nullptr;
     int device = 0;
     bool pending = false;
+    // buf holds at least `count` elements. A buffer is reallocated only once the kernels of the
+    // workspace's previous user are done: the host waits for them when, and only when, buf grows.
+    template <class T>
+    void reserve(DevBuf<T> &buf, size_t count) {
+        if (buf.n >= count) return;
+        if (pending) MPSS_HIP(hipEventSynchronize(done));
+        buf.alloc(count);
+    }
     ~RenderWorkspace();
 };
 
@@ -135,7 +142,7 @@ public:
     }
     const mpss_config &config() const { return cfg_; }
 
-    // scene + per-pixel path (render_host.cpp)
+    // scene + per-pixel path (render_host.hip)
     void add_mesh(uint32_t nv, const float *P, const float *N, const float *S, const float *uv, uint32_t nt,
                   const int32_t *idx, const float *o2w, const float *w2o, bool reverse, uint32_t material);
     void add_sphere_light(const float *c, float r, const float *Lemit, int nsamples);
@@ -226,6 +233,17 @@ private:
     // of samples whose camera ray hits (all a render reads)
     void replay_window(RenderWorkspace *ws, const RenderScene &sc, int spp, int x0, int x1, int y0, int y1,
                        hipStream_t stream, bool all_values = false);
+    // The steps of one render_tiles batch, in order (render_host.hip; mu_ not held). A TileCall is the
+    // call's constants: stream, workspace, sampling and instrumentation settings, BSSRDF materials.
+    struct TileCall;
+    void batch_begin(const TileCall &c, int64_t total);
+    void batch_window(TileCall &c, RenderScene &sc, const PlanBatch &b);
+    void launch_pieces(const TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, bool film);
+    int batch_primary(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b);
+    void batch_reserve_hits(const TileCall &c, const RenderScene &sc, int64_t nh);
+    void batch_direct(TileCall &c, const RenderScene &sc, int64_t nh);
+    void batch_mo(TileCall &c, int64_t nh);
+    void batch_film(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, int64_t nh);
     SceneData scene_;
     bool scene_dirty_ = true, materials_dirty_ = false;
     // where points_ came from: the caller (set_surface_points / pointsfile) or a Preprocess of this

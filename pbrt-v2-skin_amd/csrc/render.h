@@ -10,6 +10,7 @@
 #include "replay.h"
 #include "scene.h"
 #include "texture.h"
+#include "tile_plan.h"
 
 namespace mpss {
 
@@ -120,20 +121,10 @@ void replay_window_tasks(int xres, int yres, int ntasks, int x0, int x1, int y0,
 // IrradianceTask streams: scr[(i * nlights + l) * 2 + {0, 1}] for points i < n
 __global__ void replay_irradiance_kernel(int n, int nlights, int ntasks, uint32_t *mt, uint32_t *scr);
 
-// A tile [x0,x1) x [y0,y1) extended by one pixel on every side that exists (origin ex0, ey0;
-// ew x eh pixels): a sample whose float image coordinate rounds onto a pixel edge also lands
-// in the neighbouring pixel (film_kernel).
-struct TileBatch {
-    int x0, x1, y0, y1, ex0, ey0, ew, eh, spp;
-    uint32_t seed;
-    int64_t nsamples;  // ew * eh * spp
-};
-
-// Up to kMaxPieces tile pieces of one batch in ONE launch of primary_kernel / film_kernel (a
-// launch per piece left most of the chip idle: a 128 x 128 tile's film pass is 64 workgroups).
-// Piece k owns blocks [block0[k], block0[k + 1]); its camera samples start at record off[k] of
-// the batch; out[k] / out_stride[k]: its film rectangle (film_kernel).
-constexpr int kMaxPieces = 16;
+// Up to kMaxPieces tile pieces (TileBatch, tile_plan.h) of one batch in ONE launch of primary_kernel /
+// film_kernel (a launch per piece left most of the chip idle: a 128 x 128 tile's film pass is 64
+// workgroups). Piece k owns blocks [block0[k], block0[k + 1]); its camera samples start at record
+// off[k] of the batch; out[k] / out_stride[k]: its film rectangle (film_kernel).
 struct PieceList {
     int n;
     int block0[kMaxPieces + 1];

@@ -1,4 +1,4 @@
-// render_host.cpp -- host driver of the per-pixel path: scene upload, Preprocess
+// render_host.hip -- host driver of the per-pixel path: scene upload, Preprocess
 // (tessellation -> irradiance kernel -> octree) and tiled rendering (render.hip kernels).
 #include <algorithm>
 #include <cmath>
@@ -14,11 +14,6 @@
 namespace mpss {
 
 namespace {
-int round_up_pow2(int v) {
-    int r = 1;
-    while (r < v) r <<= 1;
-    return r;
-}
 float det3(const float *m) {
     return m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) +
            m[2] * (m[4] * m[9] - m[5] * m[8]);
@@ -228,8 +223,8 @@ void Context::upload_scene() {
             r.mint = em.mint;
             r.s.r = 0.f;
         }
-        r.nsamples_pow2 = round_up_pow2(l.nsamples);
-        r.nsamples_round = round_up_pow2(l.nsamples);
+        r.nsamples_pow2 = replay_round_up_pow2(l.nsamples);
+        r.nsamples_round = replay_round_up_pow2(l.nsamples);
         r.replay_off = replay_off;
         replay_off += kReplayPerLightSample * r.nsamples_round;
         rl.push_back(r);
@@ -602,13 +597,6 @@ void Context::find_poisson_points(uint32_t seed) {
     }
 }
 
-// SamplerRenderer::Render restricted to pixel rectangles. Each rectangle is cut into row
-// pieces (a piece = the rows plus a one-pixel border of samples that the box filter carries
-// in); pieces are packed into batches of <= max_batch_samples camera samples. Per batch:
-// camera/direct kernel per piece (all pieces append their surface hits to one compacted
-// list) -> ONE sharded Mo() gather per BSSRDF material over the batch's hits -> film kernel per
-// piece. Calls on different streams may overlap: each takes its own workspace (RenderWorkspace),
-// and the scene, materials and octree are only read after the context lock is released.
 // The reference sampler's values over [x0, x1) x [y0, y1) of the sample extent at `spp`
 // (replay_gen.hip) into ws->rp_table, continuing the workspace's task streams.
 void Context::replay_window(RenderWorkspace *ws, const RenderScene &sc, int spp, int x0, int x1, int y0, int y1,
@@ -618,20 +606,13 @@ void Context::replay_window(RenderWorkspace *ws, const RenderScene &sc, int spp,
     const uint64_t key[3] = {scene_gen_, (uint64_t)spp, (uint64_t)T};
     if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));  // the workspace's previous user
     if (ws->rp_key[0] != key[0] || ws->rp_key[1] != key[1] || ws->rp_key[2] != key[2]) {
-        if ((int64_t)ws->rp_pix.n < T) {
-            if (ws->pending) MPSS_HIP(hipEventSynchronize(ws->done));
-            ws->rp_mt.alloc((size_t)624 * T);
-            ws->rp_pix.alloc((size_t)T);
-            ws->rp_mti.alloc((size_t)T);
-        }
+        ws->reserve(ws->rp_mt, (size_t)624 * T);
+        ws->reserve(ws->rp_pix, (size_t)T);
+        ws->reserve(ws->rp_mti, (size_t)T);
         MPSS_HIP(hipMemsetAsync(ws->rp_pix.ptr, 0xff, sizeof(int) * (size_t)T, stream));  // -1: not seeded
         for (int k = 0; k < 3; ++k) ws->rp_key[k] = key[k];
     }
-    const size_t need = (size_t)(x1 - x0) * (y1 - y0) * spp * replay_k_;
-    if (ws->rp_table.n < need) {
-        if (ws->pending) MPSS_HIP(hipEventSynchronize(ws->done));
-        ws->rp_table.alloc(need);
-    }
+    ws->reserve(ws->rp_table, (size_t)(x1 - x0) * (y1 - y0) * spp * replay_k_);
     ReplayWindow w{};
     replay_window_tasks(W, H, T, x0, x1, y0, y1, w);
     w.spp = spp;
@@ -641,7 +622,7 @@ void Context::replay_window(RenderWorkspace *ws, const RenderScene &sc, int spp,
     w.nlights = (int)scene_.lights.size();
     w.arr_draws = 0;
     for (const SceneLight &l : scene_.lights) {
-        const int n = round_up_pow2(l.nsamples);
+        const int n = replay_round_up_pow2(l.nsamples);
         w.nmax = std::max(w.nmax, n);
         w.arr_draws += 3 * (spp * n + spp) + 5;
     }
@@ -670,7 +651,7 @@ void Context::replay_samples(int spp, float *out, uint64_t *n_floats, int *k) {
     sync_scene_locked();
     const int W = scene_.camera.xres, H = scene_.camera.yres;
     if (W <= 0) throw Error(MPSS_ERR_INVALID, "replay_samples: no camera");
-    spp = round_up_pow2(spp);
+    spp = replay_round_up_pow2(spp);
     if (spp > kReplayMaxSpp) throw Error(MPSS_ERR_INVALID, "replay_samples: spp too large for the replay sampler");
     check_replay_lds(spp, "replay_samples");
     const int K = replay_k_;
@@ -695,6 +676,184 @@ void Context::replay_samples(int spp, float *out, uint64_t *n_floats, int *k) {
             for (int c = 0; c < K; ++c) out[(p * spp + s2) * K + c] = col[((size_t)c * npix + p) * spp + s2];
 }
 
+// One render_tiles call's constants, as its batch steps read them (mu_ not held: what they name of the
+// context -- scene buffers, materials, octree -- is only read).
+struct Context::TileCall {
+    hipStream_t stream;
+    RenderWorkspace *ws;
+    float *const *outs;  // per rectangle
+    int spp;
+    uint32_t seed;
+    int nlights, ns_max;
+    bool timing;
+    unsigned long long *counts;  // traversal counters (null: not counting)
+    // every LayeredSkin material has a MultipoleBSSRDF (GetMultipoleBSSRDF, layeredskin.cpp:180-185):
+    // each evaluates Mo() with its own profile (multipolesubsurface.cpp:267-280)
+    struct SssMat {
+        int id;
+        const Material *m;
+        const BandLayout *layout;
+    };
+    std::vector<SssMat> sss;
+    float max_error;
+    GatherOpts gopts;
+    std::vector<Timed> timed;
+    // (the per-hit pointers are valid after batch_reserve_hits)
+    SampleRecs recs() const {
+        return SampleRecs{ws->flags.ptr, ws->spill.ptr, ws->slot.ptr, ws->ld.ptr, ws->ha.ptr, ws->hb.ptr, ws->hs.ptr,
+                          ws->q.ptr,     ws->count.ptr, ws->mo.ptr,   ws->xyz.ptr, ws->alb.ptr, ws->frame.ptr};
+    }
+};
+
+// per-sample buffers: the batch's camera samples (primary_kernel may give each a hit slot)
+void Context::batch_begin(const TileCall &c, int64_t total) {
+    RenderWorkspace *ws = c.ws;
+    ws->reserve(ws->flags, (size_t)total);
+    ws->reserve(ws->slot, (size_t)total);
+    ws->reserve(ws->ha, (size_t)total);
+    ws->reserve(ws->hb, (size_t)total);
+    ws->reserve(ws->hs, (size_t)total);
+    ws->reserve(ws->spill, (size_t)(total / c.spp));
+    MPSS_HIP(hipMemsetAsync(ws->count.ptr, 0, sizeof(int), c.stream));
+    MPSS_HIP(hipMemsetAsync(ws->spill.ptr, 0, sizeof(uint32_t) * (size_t)(total / c.spp), c.stream));
+}
+
+// replay: the reference sampler's values over the batch's window, when the plan starts a new one
+void Context::batch_window(TileCall &c, RenderScene &sc, const PlanBatch &b) {
+    if (!b.new_window) return;
+    hipEvent_t ev{};
+    time_begin(c.timing, c.stream, ev);
+    replay_window(c.ws, sc, c.spp, b.wx0, b.wx1, b.wy0, b.wy1, c.stream);
+    time_end(c.timing, c.stream, ev, 6, c.timed);
+    sc.replay = c.ws->rp_table.ptr;
+    sc.replay_x0 = b.wx0;
+    sc.replay_y0 = b.wy0;
+    sc.replay_w = b.wx1 - b.wx0;
+    sc.replay_npix = (int64_t)(b.wx1 - b.wx0) * (b.wy1 - b.wy0);
+}
+
+// the batch's pieces, kMaxPieces per launch, through primary_kernel or film_kernel
+void Context::launch_pieces(const TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b,
+                            bool film) {
+    for (const LaunchGroup &g : launch_groups(plan, b, film)) {
+        PieceList pl{};
+        pl.n = g.n;
+        for (int j = 0; j < g.n; ++j) {
+            const PlanPiece &p = plan.pieces[g.first + j];
+            pl.block0[j] = g.block0[j];
+            pl.tb[j] = p.tb;
+            pl.off[j] = g.off[j];
+            pl.out[j] = c.outs[p.rect] + p.out_off;
+            pl.out_stride[j] = g.out_stride[j];
+        }
+        pl.block0[g.n] = g.blocks;
+        if (film)
+            hipLaunchKernelGGL(film_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs());
+        else
+            hipLaunchKernelGGL(primary_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs());
+    }
+}
+
+// primary_kernel over the batch; returns the batch's hit count, which sizes everything after the
+// compaction: one read-back per batch (the stream only waits for primary_kernel; the GPU idles for the
+// round trip alone)
+int Context::batch_primary(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b) {
+    hipEvent_t ev{};
+    time_begin(c.timing, c.stream, ev);
+    launch_pieces(c, sc, plan, b, false);
+    time_end(c.timing, c.stream, ev, 1, c.timed);
+    int nh_dev = 0;
+    MPSS_HIP(hipMemcpyAsync(&nh_dev, c.ws->count.ptr, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    MPSS_HIP(hipStreamSynchronize(c.stream));
+    return nh_dev;
+}
+
+// per-hit buffers: Mo() queries and results, direct light, XYZ, the gather's query order, texture lookups
+void Context::batch_reserve_hits(const TileCall &c, const RenderScene &sc, int64_t nh) {
+    RenderWorkspace *ws = c.ws;
+    ws->reserve(ws->q, (size_t)nh);
+    ws->reserve(ws->xyz, (size_t)nh);
+    ws->reserve(ws->mo, (size_t)nh * kGroups);
+    ws->reserve(ws->ld, (size_t)nh * ROW);
+    ws->reserve(ws->perm, (size_t)((nh + 1023) / 1024 * 1024));
+    if (sc.any_tex) {
+        ws->reserve(ws->alb, (size_t)nh);
+        ws->reserve(ws->frame, (size_t)nh * 2);
+    }
+}
+
+// texture lookups, then UniformSampleAllLights: a lane per (hit, light, light sample), combined per hit
+void Context::batch_direct(TileCall &c, const RenderScene &sc, int64_t nh) {
+    RenderWorkspace *ws = c.ws;
+    const hipStream_t stream = c.stream;
+    const int64_t lanes = nh * std::max<int64_t>(1, (int64_t)c.nlights) * c.ns_max;
+    if (lanes > (int64_t)INT32_MAX)
+        throw Error(MPSS_ERR_INVALID, "render_tile: too many light samples per batch; lower "
+                                      "max_batch_samples");
+    ws->reserve(ws->terms, (size_t)lanes * 64);
+    DirectTerms *terms = reinterpret_cast<DirectTerms *>(ws->terms.ptr);
+    float4 *inf_st = nullptr;
+    if (sc.n_infinite > 0) {
+        ws->reserve(ws->st, (size_t)lanes);
+        inf_st = ws->st.ptr;
+    }
+    const SampleRecs rec = c.recs();
+    const dim3 per_hit((unsigned)((nh + 255) / 256));
+    hipEvent_t ev{};
+    if (sc.any_tex) {
+        time_begin(c.timing, stream, ev);
+        hipLaunchKernelGGL(shade_tex_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh);
+        time_end(c.timing, stream, ev, 5, c.timed);
+    }
+    time_begin(c.timing, stream, ev);
+    if (c.nlights > 0) {
+        hipLaunchKernelGGL(shade_direct_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, sc, rec,
+                           c.spp, c.seed, (int)nh, c.ns_max, terms, inf_st);
+        if (sc.n_infinite > 0)
+            hipLaunchKernelGGL(direct_combine_kernel<true>, per_hit, dim3(256), 0, stream, sc, rec, (int)nh, c.ns_max,
+                               (const DirectTerms *)terms, (const float4 *)inf_st);
+        else
+            hipLaunchKernelGGL(direct_combine_kernel<false>, per_hit, dim3(256), 0, stream, sc, rec, (int)nh, c.ns_max,
+                               (const DirectTerms *)terms, (const float4 *)nullptr);
+    } else {
+        hipLaunchKernelGGL(shade_nolight_kernel, per_hit, dim3(256), 0, stream, sc, rec, (int)nh);
+    }
+    time_end(c.timing, stream, ev, 4, c.timed);
+}
+
+// ONE sharded Mo() gather per BSSRDF material over the batch's hits
+void Context::batch_mo(TileCall &c, int64_t nh) {
+    if (c.sss.empty()) return;
+    RenderWorkspace *ws = c.ws;
+    hipEvent_t ev{};
+    time_begin(c.timing, c.stream, ev);
+    for (const TileCall::SssMat &s : c.sss)  // (an rgbprofile material: FromRGB of its R, G, B lookups)
+        launch_mo_band(dev_octree_, *s.layout, s.m->dev_profile, c.max_error, (int)nh, ws->q.ptr, ws->count.ptr,
+                       ws->mo.ptr, c.sss.size() > 1 ? ws->hs.ptr : nullptr, s.id, c.counts, ws->work.ptr, ws->perm.ptr,
+                       c.gopts, c.stream);
+    time_end(c.timing, c.stream, ev, 2, c.timed);
+}
+
+// Li assembly per hit, the sky behind the misses, then the box-filtered film per piece
+void Context::batch_film(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, int64_t nh) {
+    const SampleRecs rec = c.recs();
+    const dim3 per_hit((unsigned)((nh + 255) / 256));
+    hipEvent_t ev{};
+    time_begin(c.timing, c.stream, ev);
+    hipLaunchKernelGGL(assemble_kernel, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+    if (sc.n_infinite > 0) hipLaunchKernelGGL(sky_kernel, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+    launch_pieces(c, sc, plan, b, true);
+    time_end(c.timing, c.stream, ev, 3, c.timed);
+    MPSS_HIP(hipGetLastError());
+}
+
+// SamplerRenderer::Render restricted to pixel rectangles. plan_tiles (tile_plan.h) cuts each rectangle
+// into row pieces (a piece = the rows plus a one-pixel border of samples that the box filter carries
+// in) and packs the pieces into batches of <= max_batch_samples camera samples. Per batch:
+// camera kernel over the pieces (all pieces append their surface hits to one compacted list) -> direct
+// lighting per hit -> ONE sharded Mo() gather per BSSRDF material over the batch's hits -> film kernel
+// over the pieces. Calls on different streams may overlap: each takes its own workspace (RenderWorkspace),
+// and the scene, materials and octree are only read after the context lock is released.
 void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, float *const *outs,
                            hipStream_t stream) {
     activate();
@@ -706,309 +865,68 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
     if (spp < 1 || spp > 65535) throw Error(MPSS_ERR_INVALID, "render_tile: spp must be in [1, 65535]");
     const bool replay = cfg_.sampler == MPSS_SAMPLER_REFERENCE;
     if (replay) {
-        spp = round_up_pow2(spp);  // LDSampler rounds pixelsamples up (lowdiscrepancy.cpp:45-49)
+        spp = replay_round_up_pow2(spp);  // LDSampler rounds pixelsamples up (lowdiscrepancy.cpp:45-49)
         if (spp > kReplayMaxSpp)
             throw Error(MPSS_ERR_INVALID, "render_tile: spp must be at most 4096 for the replay sampler");
         check_replay_lds(spp, "render_tile");
     }
     for (int i = 0; i < n; ++i) {
-        const int32_t *r = rects + 4 * i;
-        if (r[0] < 0 || r[2] < 0 || r[1] > W || r[3] > H || r[0] >= r[1] || r[2] >= r[3])
-            throw Error(MPSS_ERR_INVALID, "render_tile: bad rectangle");
+        if (!tile_rect_ok(rects + 4 * i, W, H)) throw Error(MPSS_ERR_INVALID, "render_tile: bad rectangle");
         if (!outs[i]) throw Error(MPSS_ERR_INVALID, "render_tile: null output");
     }
-    // every LayeredSkin material has a MultipoleBSSRDF (GetMultipoleBSSRDF, layeredskin.cpp:180-185):
-    // each evaluates Mo() with its own profile (multipolesubsurface.cpp:267-280)
-    struct SssMat {
-        int id;
-        const Material *m;
-        const BandLayout *layout;
-    };
-    std::vector<SssMat> sss;
+    TileCall c{};
+    c.stream = stream;
+    c.outs = outs;
+    c.spp = spp;
+    c.seed = seed;
     if (have_octree_)
         for (size_t i = 0; i < materials_.size(); ++i)
             if (!materials_[i]->dipole && !materials_[i]->no_bssrdf)
-                sss.push_back(SssMat{(int)i, materials_[i].get(),
-                                     &dev_octree_.ensure_layout(materials_[i]->dev_profile.groups)});
+                c.sss.push_back(TileCall::SssMat{(int)i, materials_[i].get(),
+                                                 &dev_octree_.ensure_layout(materials_[i]->dev_profile.groups)});
     RenderScene sc = render_scene();
-    sc.have_octree = sss.empty() ? 0 : 1;
-    if (replay) {  // (the window and its table: per batch, below)
+    sc.have_octree = c.sss.empty() ? 0 : 1;
+    if (replay) {  // (the window and its table: per batch, batch_window)
         sc.replay_k = replay_k_;
         sc.replay_spp = spp;
     }
-    const bool timing = cfg_.kernel_timing != 0, counting = cfg_.count_traversal != 0;
+    const bool counting = cfg_.count_traversal != 0;
+    c.timing = cfg_.kernel_timing != 0;
     if (counting && !d_counts_.ptr) {
         d_counts_.alloc(kStatStride * kGroups);
         MPSS_HIP(hipMemset(d_counts_.ptr, 0, kStatStride * kGroups * sizeof(unsigned long long)));
     }
-    unsigned long long *const counts = counting ? d_counts_.ptr : nullptr;
+    c.counts = counting ? d_counts_.ptr : nullptr;
     const int64_t max_batch = std::max<int64_t>(cfg_.max_batch_samples, 1 << 10);
-    const int nlights = (int)scene_.lights.size();
-    int ns_max = 1;
-    for (const SceneLight &l : scene_.lights) ns_max = std::max(ns_max, round_up_pow2(l.nsamples));
-    const float max_error = max_error_;
-    const GatherOpts gopts = gather_opts();
-    RenderWorkspace *ws = acquire_ws();
+    c.nlights = (int)scene_.lights.size();
+    c.ns_max = 1;
+    for (const SceneLight &l : scene_.lights) c.ns_max = std::max(c.ns_max, replay_round_up_pow2(l.nsamples));
+    c.max_error = max_error_;
+    c.gopts = gather_opts();
+    const int replay_k = replay_k_;
+    RenderWorkspace *ws = c.ws = acquire_ws();
     ++inflight_;  // until this call's kernels are queued (see quiesce_locked)
     lk.unlock();
     InflightGuard guard{this, ws, stream};  // every way out: workspace back to the pool, inflight_ down
 
-    std::vector<Timed> timed;
+    const TilePlan plan = plan_tiles(W, H, spp, seed, n, rects, max_batch, replay, replay_k, kReplayWindowFloats);
     int64_t n_samples = 0, n_sss = 0;
-    {
-        if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));
-        // a workspace buffer is reallocated only once its previous user's kernels are done
-        auto grow = [&](auto &buf, int64_t &have, int64_t want, size_t per) {
-            if (have >= want) return;
-            if (ws->pending) MPSS_HIP(hipEventSynchronize(ws->done));
-            buf.alloc((size_t)want * per);
-            have = want;
-        };
-        // cut rectangles into pieces of <= max_batch samples
-        struct Piece {
-            TileBatch tb;
-            float *out;
-        };
-        std::vector<Piece> pieces;
-        // replay: rectangles in row order, so that consecutive batches continue the task streams
-        // (replay_window) and a batch's window stays compact
-        std::vector<int> order(n);
-        for (int i = 0; i < n; ++i) order[i] = i;
-        if (replay)
-            std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-                return rects[4 * a + 2] != rects[4 * b + 2] ? rects[4 * a + 2] < rects[4 * b + 2]
-                                                            : rects[4 * a] < rects[4 * b];
-            });
-        for (int i : order) {
-            const int x0 = rects[4 * i], x1 = rects[4 * i + 1], y0 = rects[4 * i + 2], y1 = rects[4 * i + 3];
-            const int tw = x1 - x0;
-            const int ex0 = std::max(x0 - 1, 0);
-            const int ew = std::min(x1 + 1, W) - ex0;
-            const int rows = (int)std::max<int64_t>(1, max_batch / ((int64_t)ew * spp) - 2);
-            for (int yb = y0; yb < y1; yb += rows) {
-                const int ye = std::min(y1, yb + rows);
-                Piece p;
-                p.tb.x0 = x0;
-                p.tb.x1 = x1;
-                p.tb.y0 = yb;
-                p.tb.y1 = ye;
-                p.tb.ex0 = ex0;
-                p.tb.ey0 = std::max(yb - 1, 0);
-                p.tb.ew = ew;
-                p.tb.eh = std::min(ye + 1, H) - p.tb.ey0;
-                p.tb.spp = spp;
-                p.tb.seed = seed;
-                p.tb.nsamples = (int64_t)p.tb.ew * p.tb.eh * spp;
-                p.out = outs[i] + (size_t)(yb - y0) * tw * 4;
-                pieces.push_back(p);
-            }
-        }
-        size_t pi = 0;
-        // replay: the current generated window (it may span several batches: one generation over
-        // more tasks keeps more waves in flight, replay_gen.hip)
-        bool have_win = false;
-        int wx0 = 0, wx1 = 0, wy0 = 0, wy1 = 0;
-        while (pi < pieces.size()) {
-            // pack pieces into one batch
-            size_t pe = pi;
-            int64_t total = 0;
-            // replay: the batch's window (the pieces' bounding box) holds spp x replay_k_ floats per
-            // pixel; kept to <= kReplayWindowFloats
-            int bx0 = INT32_MAX, bx1 = 0, by0 = INT32_MAX, by1 = 0;
-            auto fits = [&](const TileBatch &tb) {
-                if (!replay) return true;
-                const int64_t w = std::max(bx1, tb.ex0 + tb.ew) - std::min(bx0, tb.ex0);
-                const int64_t h = std::max(by1, tb.ey0 + tb.eh) - std::min(by0, tb.ey0);
-                return w * h * spp * replay_k_ <= kReplayWindowFloats;
-            };
-            while (pe < pieces.size() &&
-                   (pe == pi || (total + pieces[pe].tb.nsamples <= max_batch && fits(pieces[pe].tb)))) {
-                const TileBatch &tb = pieces[pe].tb;
-                bx0 = std::min(bx0, tb.ex0);
-                bx1 = std::max(bx1, tb.ex0 + tb.ew);
-                by0 = std::min(by0, tb.ey0);
-                by1 = std::max(by1, tb.ey0 + tb.eh);
-                total += pieces[pe++].tb.nsamples;
-            }
-            // per-sample buffers: the batch's camera samples (primary_kernel may give each a hit slot)
-            if (ws->n < total) {
-                int64_t have = ws->n;
-                grow(ws->flags, have, total, 1);
-                have = ws->n;
-                grow(ws->slot, have, total, 1);
-                ws->n = total;
-            }
-            if (ws->rec_n < total) {
-                for (auto *b : {&ws->ha, &ws->hb}) {
-                    int64_t have = ws->rec_n;
-                    grow(*b, have, total, 1);
-                }
-                int64_t have = ws->rec_n;
-                grow(ws->hs, have, total, 1);
-                ws->rec_n = total;
-            }
-            if (ws->px < total / spp) {
-                int64_t have = ws->px;
-                grow(ws->spill, have, total / spp, 1);
-                ws->px = total / spp;
-            }
-            MPSS_HIP(hipMemsetAsync(ws->count.ptr, 0, sizeof(int), stream));
-            MPSS_HIP(hipMemsetAsync(ws->spill.ptr, 0, sizeof(uint32_t) * (size_t)(total / spp), stream));
-            auto recs = [&](int64_t off) {  // (the per-hit pointers are read after the hit-count resize)
-                return SampleRecs{ws->flags.ptr + off, ws->spill.ptr + off / spp, ws->slot.ptr + off, ws->ld.ptr,
-                                  ws->ha.ptr, ws->hb.ptr, ws->hs.ptr, ws->q.ptr, ws->count.ptr, ws->mo.ptr,
-                                  ws->xyz.ptr, ws->alb.ptr, ws->frame.ptr};
-            };
-            // the batch's pieces, kMaxPieces per launch; blocks per piece: samples (primary) or
-            // tile pixels (film) / 256
-            auto launch_pieces = [&](bool film) {
-                int64_t off = 0;
-                for (size_t k0 = pi; k0 < pe; k0 += kMaxPieces) {
-                    PieceList pl{};
-                    int blocks = 0;
-                    for (size_t k = k0; k < pe && k < k0 + kMaxPieces; ++k) {
-                        const TileBatch &tb = pieces[k].tb;
-                        const int j = pl.n++;
-                        const int tw = tb.x1 - tb.x0;
-                        const int64_t items = film ? (int64_t)tw * (tb.y1 - tb.y0) : tb.nsamples;
-                        pl.block0[j] = blocks;
-                        pl.tb[j] = tb;
-                        pl.off[j] = off;
-                        pl.out[j] = pieces[k].out;
-                        pl.out_stride[j] = tw;
-                        blocks += (int)((items + 255) / 256);
-                        off += tb.nsamples;
-                    }
-                    pl.block0[pl.n] = blocks;
-                    if (film)
-                        hipLaunchKernelGGL(film_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sc, pl, recs(0));
-                    else
-                        hipLaunchKernelGGL(primary_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, sc, pl,
-                                           recs(0));
-                }
-            };
-            hipEvent_t ev{};
-            if (replay && (!have_win || bx0 < wx0 || bx1 > wx1 || by0 < wy0 || by1 > wy1)) {
-                // the reference sampler's values over a new window: this batch's pieces and the
-                // following ones, as far as the window table allows (kReplayWindowFloats)
-                int gx0 = bx0, gx1 = bx1, gy0 = by0, gy1 = by1;
-                for (size_t k = pe; k < pieces.size(); ++k) {
-                    const TileBatch &tb = pieces[k].tb;
-                    const int nx0 = std::min(gx0, tb.ex0), nx1 = std::max(gx1, tb.ex0 + tb.ew);
-                    const int ny0 = std::min(gy0, tb.ey0), ny1 = std::max(gy1, tb.ey0 + tb.eh);
-                    if ((int64_t)(nx1 - nx0) * (ny1 - ny0) * spp * replay_k_ > kReplayWindowFloats) break;
-                    gx0 = nx0;
-                    gx1 = nx1;
-                    gy0 = ny0;
-                    gy1 = ny1;
-                }
-                time_begin(timing, stream, ev);
-                replay_window(ws, sc, spp, gx0, gx1, gy0, gy1, stream);
-                time_end(timing, stream, ev, 6, timed);
-                have_win = true;
-                wx0 = gx0;
-                wx1 = gx1;
-                wy0 = gy0;
-                wy1 = gy1;
-                sc.replay = ws->rp_table.ptr;
-                sc.replay_x0 = wx0;
-                sc.replay_y0 = wy0;
-                sc.replay_w = wx1 - wx0;
-                sc.replay_npix = (int64_t)(wx1 - wx0) * (wy1 - wy0);
-            }
-            time_begin(timing, stream, ev);
-            launch_pieces(false);
-            time_end(timing, stream, ev, 1, timed);
-            // the batch's hit count sizes everything after the compaction: one read-back per batch
-            // (the stream only waits for primary_kernel; the GPU idles for the round trip alone)
-            int nh_dev = 0;
-            MPSS_HIP(hipMemcpyAsync(&nh_dev, ws->count.ptr, sizeof(int), hipMemcpyDeviceToHost, stream));
-            MPSS_HIP(hipStreamSynchronize(stream));
-            const int64_t nh = std::max<int64_t>(1, nh_dev);
-            if (ws->hits < nh) {
-                for (auto *b : {&ws->q, &ws->xyz}) {
-                    int64_t have = ws->hits;
-                    grow(*b, have, nh, 1);
-                }
-                int64_t have = ws->hits;
-                grow(ws->mo, have, nh, kGroups);
-                have = ws->hits;
-                grow(ws->ld, have, nh, ROW);
-                ws->hits = nh;
-            }
-            grow(ws->perm, ws->perm_n, (nh + 1023) / 1024 * 1024, 1);
-            if (sc.any_tex && ws->tex_hits < nh) {
-                int64_t have = ws->tex_hits;
-                grow(ws->alb, have, nh, 1);
-                have = ws->tex_hits;
-                grow(ws->frame, have, nh, 2);
-                ws->tex_hits = nh;
-            }
-            {
-                const SampleRecs rec = recs(0);
-                const int64_t lanes = nh * std::max<int64_t>(1, (int64_t)nlights) * ns_max;
-                if (lanes > (int64_t)INT32_MAX)
-                    throw Error(MPSS_ERR_INVALID, "render_tile: too many light samples per batch; lower "
-                                                  "max_batch_samples");
-                grow(ws->terms, ws->terms_n, lanes, 64);
-                DirectTerms *terms = reinterpret_cast<DirectTerms *>(ws->terms.ptr);
-                float4 *inf_st = nullptr;
-                if (sc.n_infinite > 0) {
-                    grow(ws->st, ws->st_n, lanes, 1);
-                    inf_st = ws->st.ptr;
-                }
-                if (sc.any_tex) {
-                    time_begin(timing, stream, ev);
-                    hipLaunchKernelGGL(shade_tex_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, stream, sc,
-                                       rec, spp, seed, (int)nh);
-                    time_end(timing, stream, ev, 5, timed);
-                }
-                time_begin(timing, stream, ev);
-                if (nlights > 0) {
-                    hipLaunchKernelGGL(shade_direct_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0,
-                                       stream, sc, rec, spp, seed, (int)nh, ns_max, terms, inf_st);
-                    if (sc.n_infinite > 0)
-                        hipLaunchKernelGGL(direct_combine_kernel<true>, dim3((unsigned)((nh + 255) / 256)), dim3(256),
-                                           0, stream, sc, rec, (int)nh, ns_max, (const DirectTerms *)terms,
-                                           (const float4 *)inf_st);
-                    else
-                        hipLaunchKernelGGL(direct_combine_kernel<false>, dim3((unsigned)((nh + 255) / 256)), dim3(256),
-                                           0, stream, sc, rec, (int)nh, ns_max, (const DirectTerms *)terms,
-                                           (const float4 *)nullptr);
-                } else {
-                    hipLaunchKernelGGL(shade_nolight_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, stream,
-                                       sc, rec, (int)nh);
-                }
-                time_end(timing, stream, ev, 4, timed);
-            }
-            if (!sss.empty()) {
-                time_begin(timing, stream, ev);
-                for (const SssMat &s : sss)  // (an rgbprofile material: FromRGB of its R, G, B lookups)
-                    launch_mo_band(dev_octree_, *s.layout, s.m->dev_profile, max_error, (int)nh, ws->q.ptr,
-                                   ws->count.ptr, ws->mo.ptr, sss.size() > 1 ? ws->hs.ptr : nullptr, s.id, counts,
-                                   ws->work.ptr, ws->perm.ptr, gopts, stream);
-                time_end(timing, stream, ev, 2, timed);
-            }
-            time_begin(timing, stream, ev);
-            {
-                const SampleRecs rec = recs(0);
-                hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, stream, sc, rec,
-                                   (int)nh);
-                if (sc.n_infinite > 0)
-                    hipLaunchKernelGGL(sky_kernel, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, stream, sc, rec,
-                                       (int)nh);
-            }
-            launch_pieces(true);
-            time_end(timing, stream, ev, 3, timed);
-            MPSS_HIP(hipGetLastError());
-            n_samples += total;
-            if (counting) n_sss += nh_dev;
-            pi = pe;
-        }
+    if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));
+    for (const PlanBatch &b : plan.batches) {
+        batch_begin(c, b.total);
+        batch_window(c, sc, b);
+        const int nh_dev = batch_primary(c, sc, plan, b);
+        const int64_t nh = std::max<int64_t>(1, nh_dev);
+        batch_reserve_hits(c, sc, nh);
+        batch_direct(c, sc, nh);
+        batch_mo(c, nh);
+        batch_film(c, sc, plan, b, nh);
+        n_samples += b.total;
+        if (counting) n_sss += nh_dev;
     }
     guard.release();
     std::lock_guard<std::mutex> g(mu_);  // (released before the guard's end_inflight takes mu_)
-    timed_.insert(timed_.end(), timed.begin(), timed.end());
+    timed_.insert(timed_.end(), c.timed.begin(), c.timed.end());
     stats_.samples += n_samples;
     stats_.sss_samples += n_sss;
 }
@@ -1032,8 +950,7 @@ void Context::tile_costs(int n, const int32_t *rects, int64_t *sss, int64_t *sur
     MPSS_HIP(hipMemcpy(h.data(), cls.ptr, h.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) {
         const int32_t *r = rects + 4 * i;
-        if (r[0] < 0 || r[2] < 0 || r[1] > W || r[3] > H || r[0] >= r[1] || r[2] >= r[3])
-            throw Error(MPSS_ERR_INVALID, "tile_costs: bad rectangle");
+        if (!tile_rect_ok(r, W, H)) throw Error(MPSS_ERR_INVALID, "tile_costs: bad rectangle");
         int64_t a = 0, b = 0;
         for (int y = r[2]; y < r[3]; ++y)
             for (int x = r[0]; x < r[1]; ++x) {

@@ -116,3 +116,24 @@ def test_render_tiles_batching_invariance(torch_dev, small_skin, mpss, max_batch
     for r, o in zip(rects, outs):
         got[r[2]:r[3], r[0]:r[1]] = o.cpu().numpy().reshape(r[3] - r[2], r[1] - r[0], 4)
     assert np.array_equal(got, ref)
+
+
+def test_render_tiles_many_pieces_in_one_batch(torch_dev, small_skin):
+    """61 rectangles in one mpss_render_tiles call at the default max_batch_samples: one batch, launched in
+    four groups of <= 16 pieces (render.h PieceList), whose sample records continue from group to group."""
+    sc, ctx = small_skin
+    ref = render(torch_dev, ctx, sc, 0, sc.xres, 0, sc.yres, sc.spp)
+    rects = [(x, x + 8, y, y + 8) for y in range(0, 40, 8) for x in range(0, sc.xres, 8)] + [(0, sc.xres, 40, sc.yres)]
+    assert len(rects) > 2 * 16
+    outs = [torch_dev.zeros(((r[1] - r[0]) * (r[3] - r[2]) * 4,), device="cuda") for r in rects]
+    ctx.set_instrumentation(kernel_timing=True)
+    ctx.reset_render_stats()
+    ctx.render_tiles(sc.spp, 3, rects, [o.data_ptr() for o in outs])
+    torch_dev.cuda.synchronize()
+    st = ctx.render_stats()
+    ctx.set_instrumentation(False, False)
+    assert st["n_camera"] == 1  # one batch
+    got = np.zeros_like(ref)
+    for r, o in zip(rects, outs):
+        got[r[2]:r[3], r[0]:r[1]] = o.cpu().numpy().reshape(r[3] - r[2], r[1] - r[0], 4)
+    assert np.array_equal(got, ref)
