@@ -114,7 +114,7 @@ typedef struct {
                                   8 waves hide more of it (C2, round 4's first grid: 59.4 vs 68.8 ms
                                   per frame) */
     int tessellate_on_host;    /* 1: Preprocess tessellates on the host (threads over triangles,
-                                  scene.cpp); 0 (default): one GPU thread per triangle (render.hip
+                                  scene.cpp); 0 (default): one GPU thread per triangle (tess_kernel.h
                                   tess_kernel), the same points bit for bit (tessellate.h) */
     int mo_common_grid;        /* 1 (default): the sharded gather reads a band group's lookups past
                                   the exact LDS near field, as far as the resampling stays within 2e-6

@@ -1,5 +1,5 @@
 // render.h -- device-side scene, sample records and the kernels of the per-pixel path
-// (render.hip), plus the host driver that uploads a SceneData and runs Preprocess / tiles.
+// (preprocess_kernels.hip, primary.hip, shade.hip, film.hip), plus the host driver that uploads a SceneData and runs Preprocess / tiles.
 #pragma once
 #include <vector>
 
@@ -182,7 +182,7 @@ struct SampleRecs {
 };
 
 // SurfacePointTask's random-walk paths (usepoissonpointfinder): one lane per path, candidates of
-// path i at out[i * kPoissonCand ...], their count in count[i] (render.hip).
+// path i at out[i * kPoissonCand ...], their count in count[i] (preprocess_kernels.hip).
 constexpr int kPoissonDepth = 30, kPoissonCand = kPoissonDepth - 3;
 struct PoissonWalk {
     V3 origin;        // pCamera

@@ -1,5 +1,5 @@
 // render_host.hip -- host driver of the per-pixel path: scene upload, Preprocess
-// (tessellation -> irradiance kernel -> octree) and tiled rendering (render.hip kernels).
+// (tessellation -> irradiance kernel -> octree) and tiled rendering (primary.hip, shade.hip, film.hip kernels).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -63,7 +63,7 @@ void Context::add_sphere_light(const float *c, float r, const float *Lemit, int 
 
 // CreateInfiniteLight + the InfiniteAreaLight ctor without a map (lights/infinite.cpp:66-90,
 // 180-188): texels[0] = L.ToRGBSpectrum(); Le and Sample_L convert map lookups back with
-// Spectrum(rgb, SPECTRUM_ILLUMINANT) on the device (render.hip).
+// Spectrum(rgb, SPECTRUM_ILLUMINANT) on the device (spectrum_tables.h).
 void Context::add_infinite_light(const float *L, int nsamples, const float *l2w, const float *w2l, int W, int H,
                                  const float *texels) {
     std::lock_guard<std::mutex> g(mu_);

@@ -27,7 +27,7 @@
 // draws per (point, light): the Sample02 scrambles and the component scramble.
 //
 // The product replays these streams on the GPU (replay_gen.hip: one wave per render task, per
-// render batch into a table of the batch's window; render.hip replay_irradiance_kernel: one lane
+// render batch into a table of the batch's window; preprocess_kernels.hip replay_irradiance_kernel: one lane
 // per irradiance task); oracle/render.c restates the same loop on the CPU.
 #pragma once
 #include "pbrt_math.h"

@@ -355,7 +355,7 @@ __global__ __launch_bounds__(64 * kMaxWaves) void replay_window_kernel(RenderSce
         // the image samples and the camera rays (samplerrenderer.cpp:97-103): only whether they hit
         int hits = 0;
         // which of this lane's samples (lane + 64 m: bit m) hit: only those are shaded, so only their
-        // light-sample values are read (render.hip); the others' are not written unless g.all_values
+        // light-sample values are read (shade.hip); the others' are not written unless g.all_values
         uint64_t hm = 0;
         const bool traced = g.li_draws > 0 && !(skip & 4);
         for (int c = 0; c < spp; c += 64) {

@@ -2,7 +2,7 @@
 // src/shapes/trianglemesh.cpp:187-257; tessellator :265-318, matching :321-351), host and device.
 //
 // The same source runs in the host build (scene.cpp, threaded over triangles) and in the GPU
-// build (render.hip tess_kernel, one thread per triangle): the same IEEE float operations in the
+// build (tess_kernel.h, one thread per triangle): the same IEEE float operations in the
 // same order (-ffp-contract=off on both sides), so the two give the same points bit for bit.
 #pragma once
 #include "geom.h"

@@ -138,7 +138,7 @@ def scene_triangles(sc):
 
 def pixel_centre_rays(sc):
     """Camera rays through the pixel centres, row-major: origin (3,), directions (yres * xres, 3),
-    float32 and operation by operation as the tile-cost probe computes them (render.hip
+    float32 and operation by operation as the tile-cost probe computes them (primary.hip
     probe_kernel: RasterToCamera of (x + .5, y + .5, 0), divided by w, normalised by a reciprocal,
     CameraToWorld as a vector)."""
     f = np.float32

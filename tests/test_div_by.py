@@ -1,4 +1,4 @@
-"""render.hip's div_by -- IEEE x / d for 30 bands over one denominator via Markstein's correction
+"""shade.hip's div_by -- IEEE x / d for 30 bands over one denominator via Markstein's correction
 from RN(1 / d) -- must equal x / d bit for bit in its guarded range (tools/check_div.c, the same
 float operations on the host: RN(1/d), a multiply, two FMAs)."""
 import os

@@ -1,4 +1,4 @@
-"""Preprocess's point set built on the GPU (render.hip tess_kernel, one thread per triangle) against
+"""Preprocess's point set built on the GPU (tess_kernel.h, one thread per triangle) against
 the host build (scene.cpp, tessellate_on_host = 1): the same SurfacePoint records byte for byte,
 in the same order (TriangleMesh::TessellateSurfacePoints, trianglemesh.cpp:187-351, per mesh and
 triangle in order). The host build is itself bit-exact against the oracle (test_render_parity_gpu,

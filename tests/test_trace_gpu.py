@@ -1,5 +1,5 @@
-"""The four BVH tracers on the GPU (render.hip trace_closest, trace_closest_wave / _packet;
-bvh_trace.h trace_any, trace_any_wave; replay_gen.hip's copies in test_replay_gpu.py) on the hostile
+"""The four BVH tracers on the GPU (bvh_trace.h: trace_closest, trace_closest_wave / _packet,
+trace_any, trace_any_wave; replay_gen.hip's copies in test_replay_gpu.py) on the hostile
 scenes of tests/synth.py, against the oracle's tracer -- itself pinned to a float64 brute force in
 tests/test_trace_oracle.py -- and against that brute force.
 

@@ -1,4 +1,4 @@
-/* check_div.c -- render.hip's div_by (Markstein's one-FMA correction from a correctly rounded
+/* check_div.c -- shade.hip's div_by (Markstein's one-FMA correction from a correctly rounded
  * reciprocal) against IEEE x / d on random operand pairs in div_by's guarded range; prints the
  * number of differing results (must be 0). gcc -O2 -ffp-contract=off tools/check_div.c -lm */
 #include <math.h>
