@@ -142,7 +142,7 @@ public:
     }
     const mpss_config &config() const { return cfg_; }
 
-    // scene + per-pixel path (render_host.hip)
+    // scene (scene_upload.hip), Preprocess (preprocess_host.hip), tiled rendering (render_host.hip)
     void add_mesh(uint32_t nv, const float *P, const float *N, const float *S, const float *uv, uint32_t nt,
                   const int32_t *idx, const float *o2w, const float *w2o, bool reverse, uint32_t material);
     void add_sphere_light(const float *c, float r, const float *Lemit, int nsamples);
@@ -152,8 +152,8 @@ public:
     void set_camera(const float *r2c, const float *c2w, int xres, int yres);
     void set_surface_points(uint32_t n, const SurfacePoint *pts);
     void preprocess(uint32_t seed);
-    void tessellate_on_gpu();  // Preprocess point set, GPU build (render_host.hip)
-    // FindPoissonPointDistribution (usepoissonpointfinder): fills points_ (render_host.hip)
+    void tessellate_on_gpu();  // Preprocess point set, GPU build (preprocess_host.hip)
+    // FindPoissonPointDistribution (usepoissonpointfinder): fills points_ (preprocess_host.hip)
     void find_poisson_points(uint32_t seed);
     void render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, float *const *outs, hipStream_t stream);
     // the replay sampler's table (mpss_replay_samples); out may be null to query sizes
@@ -197,6 +197,12 @@ public:
 private:
     void activate() const;
     void upload_scene();
+    // its steps, in order (scene_upload.hip; mu_ held); upload_materials is the last
+    void upload_bvh();
+    void upload_camera_bins();
+    void upload_meshes();
+    void upload_lights();
+    void upload_textures();
     // the materials' device records alone (d_materials_): all a material update changes of the scene
     void upload_materials();
     // the device scene is current: upload_scene when the scene changed, upload_materials when only a
@@ -222,6 +228,11 @@ private:
     // mpss_render_tile(s) / mpss_tile_costs after a material update and before the next Preprocess
     void require_fresh_irradiance(const char *who) const;
     RenderScene render_scene() const;
+    // the steps of preprocess, in order (preprocess_host.hip; mu_ held): the point set exists, its point
+    // cache pc_ is valid, the irradiance at its n points is in irradiance_ (and dE, when a kernel ran)
+    void preprocess_points(uint32_t seed);
+    void preprocess_point_cache(int n);
+    void preprocess_irradiance(int n, uint32_t seed, float *dE);
     int first_bssrdf_material() const;
     // reference-sampler replay (mpss_config.sampler): floats per camera sample in the window tables,
     // and the scene generation the workspaces' task cursors belong to (upload_scene bumps it)
@@ -321,7 +332,7 @@ private:
     std::condition_variable_any idle_;
     void quiesce_locked();
     void end_inflight();
-    // kernel timing (cfg_.kernel_timing) and traversal counting (cfg_.count_traversal)
+    // kernel timing (cfg_.kernel_timing) and traversal counting (cfg_.count_traversal): render_stats.cpp
     struct Timed {
         hipEvent_t a, b;
         int kind;

@@ -1,5 +1,5 @@
 // envmap.h -- InfiniteAreaLight's radiance map and its sampling distribution, built on the host
-// once per light and uploaded flat (render_host.hip). Follows, in float like the reference:
+// once per light and uploaded flat (scene_upload.hip). Follows, in float like the reference:
 //   MIPMap<RGBSpectrum> ctor            core/mipmap.h:147-220 (Lanczos resampling of a non-power-
 //                                       of-two image, TEXTURE_REPEAT, box-filtered pyramid)
 //   MIPMap::Lookup(s, t, width)         core/mipmap.h:239-269 (trilinear between two levels)

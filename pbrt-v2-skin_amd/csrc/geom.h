@@ -170,6 +170,18 @@ struct SphereView {
     float theta_min, theta_max;
 };
 
+// The full sphere of radius r about c, as the Sphere ctor and Sphere::Area give its fields
+MPSS_HD SphereView full_sphere(V3 c, float r) {
+    SphereView s;
+    s.c = c;
+    s.r = r;
+    s.phi_max = (kPiF / 180.f) * 360.f;  // Radians(Clamp(360, 0, 360))
+    s.theta_min = m_acos(-1.f);          // acosf(Clamp(zmin/radius))
+    s.theta_max = m_acos(1.f);
+    s.area = s.phi_max * r * (r - -r);   // Sphere::Area
+    return s;
+}
+
 // Quadratic, core/pbrt.h:354-368
 MPSS_HD bool quadratic(float A, float B, float C, float &t0, float &t1) {
     const float disc = B * B - 4.f * A * C;

@@ -59,7 +59,7 @@ struct RenderMaterial {
 struct RenderScene {
     const BvhNode *bvh;
     // the same nodes threaded for stackless any-hit walks: an interior node's offset is the end of
-    // its pre-order subtree (render_host.hip upload_scene); nbvh nodes
+    // its pre-order subtree (scene_plain.h thread_bvh, uploaded by scene_upload.hip); nbvh nodes
     const BvhNode *bvh_thread;
     int nbvh;
     const TriRec *tris;

@@ -8,6 +8,7 @@
 
 #include "common.h"
 #include "pbrt_math.h"
+#include "scene_plain.h"  // BvhNode, thread_bvh, SurfacePoint
 
 namespace mpss {
 
@@ -39,16 +40,6 @@ struct Camera {
     int xres = 0, yres = 0;
 };
 
-// Linear BVH node (accelerators/bvh.cpp:113-123 layout): 32 B.
-struct alignas(16) BvhNode {
-    float bmin[3];
-    int32_t offset;  // leaf: first primitive; interior: second child index
-    float bmax[3];
-    uint16_t nprims;  // 0 for interior
-    uint16_t axis;
-};
-static_assert(sizeof(BvhNode) == 32, "BvhNode is 32 B");
-
 // Flattened triangle for the GPU: p1, e1 = p2-p1, e2 = p3-p1 (trianglemesh.inl:57-60) and its
 // global triangle id; 48 B.
 struct alignas(16) TriRec {
@@ -70,7 +61,7 @@ struct SceneData {
     std::vector<TriRec> tris;  // in BVH leaf order
 };
 
-void build_bvh(SceneData &s);
+void build_bvh(SceneData &s);  // (its threaded copy: thread_bvh, scene_plain.h)
 
 // Candidate triangles per pixel for the reference sampler's camera rays (replay_gen.hip: whether a
 // camera ray hits anything decides how many Li draws its sample consumes). For each pixel of the
@@ -89,14 +80,6 @@ struct CameraBins {
 constexpr double kCamBinMargin = 1.0 / 64;
 constexpr int kCamBinMaxArea = 4096;
 void build_camera_bins(const SceneData &s, CameraBins &b);
-
-// SurfacePoint (renderers/surfacepoints.h:45-55): p, n, u, v, materialId, area, rayEpsilon.
-struct SurfacePoint {
-    float p[3], n[3], u, v;
-    uint32_t material;
-    float area, ray_eps;
-};
-static_assert(sizeof(SurfacePoint) == 44, "SurfacePoint matches the reference's 44-B pointsfile record");
 
 // TriangleMesh::TessellateSurfacePoints over every mesh in order (trianglemesh.cpp:187-257,
 // tessellator 265-318, matching 321-351; driver surfacepoints.cpp:301-333).

@@ -15,7 +15,7 @@ tests/test_trace_oracle.py -- and against that brute force.
   deep trees             deep_tree(40) and deep_tree(50) -- 47 levels, the most the 48-entry traversal
                          stack allows -- pass all of the above; deep_tree(51), 48 levels, and
                          deep_tree(64) are refused on the host, naming the traversal stack, before
-                         anything is uploaded or launched (render_host.hip upload_scene). Accepting 50
+                         anything is uploaded or launched (scene_upload.hip upload_scene). Accepting 50
                          and refusing 51 pins the depth of the chain to n - 3.
 
 stacked_sheets: Preprocess starts a point's shadow rays minsampledistance / 10 off the surface, which
