@@ -1,5 +1,6 @@
 // device_profile.cpp -- DeviceProfile's host side: the profile tables' upload and the common grids built
 // from them (common_grid.h) for both LDS layouts of the sharded gather.
+#include <algorithm>
 #include <memory>
 #include <thread>
 #include <vector>
@@ -28,10 +29,8 @@ void DeviceProfile::upload(const float *tab, int len, const float *rcp_, bool sn
 }
 
 void DeviceProfile::set_rgb(const float *tab) {
-    static const float refl[7][NB] = {MPSS_BAND_RGBREFL2SPECTWHITE_INIT, MPSS_BAND_RGBREFL2SPECTCYAN_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTMAGENTA_INIT, MPSS_BAND_RGBREFL2SPECTYELLOW_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTRED_INIT, MPSS_BAND_RGBREFL2SPECTGREEN_INIT,
-                                      MPSS_BAND_RGBREFL2SPECTBLUE_INIT};
+    float refl[7][NB];
+    for (int t = 0; t < 7; ++t) std::copy_n(rgb_refl2spect(t), NB, refl[t]);
     rgb_refl.upload(&refl[0][0], 7 * NB);
     // the common grid of the R, G, B profiles (rows 0..2, the same three slots in every group: the
     // sharded gather reads them in band_tree's lband order)

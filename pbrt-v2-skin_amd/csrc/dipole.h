@@ -3,7 +3,7 @@
 //
 // It is the Rd functor the reference's dipolesubsurface integrator hands to the same
 // SubsurfaceOctreeNode::Mo (src/integrators/dipolesubsurface.cpp:171-172). Here it backs
-// "dipole" materials of mpss_mo_batch (mo_kernel.hip evaluates it per band inside the exact
+// "dipole" materials of mpss_mo_batch (mo_exact.hip evaluates it per band inside the exact
 // reference-order gather) and gives a closed-form Rd to pin the tabulated gathers against.
 //
 // Every product, quotient and sum is the reference's float operation in the reference's order

@@ -21,7 +21,7 @@
 // per-band tables (mo_common_grid 0) the L2 request rate of the per-lane table gathers alone. The traversal is the UNION of
 // the wave's 64 pruned traversals, so the 64 queries of a wave should be neighbours: each 1024-query
 // chunk is sorted by a Morton key of the query position before queries are dealt to lanes
-// (mo_kernel.hip), and the per-record work below is kept to a few VALU on 32-bit table offsets.
+// (mo_kernel.hip mo_sort_kernel), and the per-record work below is kept to a few VALU on 32-bit table offsets.
 //
 // Each query walks exactly the node set of SubsurfaceOctreeNode::Mo (diffusionutil.h:175-210)
 // minus subtrees that lie past the end of all of the group's profiles (they add +0 for these
@@ -31,6 +31,7 @@
 // each term with FMAs (cg_combine), so its sums are within the float-summation bound of the reference
 // (tests/test_mo_gpu.py) rather than bit-identical to it.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 
 #include "common.h"
@@ -83,6 +84,19 @@ struct BandTree {
     RgbK rgb_k[kGroups];    // RGB: each group's weights (band_tree, from the same tables)
 };
 
+// The limit of the exact subtree pruning, for every gather: sampleProfile returns exactly 0 once d^2 *
+// rcpDsqSpacing >= L - 1 (multipole.cpp:63-66), so a node whose box is at a squared distance d2box from
+// the query with d2box * rcp_min >= prune_f adds only +0 terms (rcp_min: the smallest rcp of the bands
+// looked up; the 1e-4 relative margin dominates the float rounding of the two distances). rcp_min <= 0
+// turns pruning off: it comes back as 0 with an infinite prune_f.
+struct PruneLimit {
+    float rcp_min, prune_f;
+};
+inline PruneLimit prune_limit(int L, float rcp_min) {
+    const float r = rcp_min > 0.f ? rcp_min : 0.f;
+    return {r, r > 0.f ? (float)(L - 1) * 1.0001f : INFINITY};
+}
+
 #ifdef __HIP__  // device traversal: HIP translation units only (host .cpp files see the layout types)
 // The lerp pair (T[s], T[s+1]) as one 8-byte load at 4-byte alignment (gfx950 global loads
 // take unaligned dword pairs): one vector-memory instruction per band instead of two.
@@ -131,6 +145,16 @@ __host__ __device__ constexpr int near_row() {
     return KLDS + 3;
 }
 
+// the per-band indices d2 * rcp_j (multipole.cpp:63: the float product)
+__device__ __forceinline__ void band_f(const BandLane &b, float d2, float f[4]) {
+    const f2v f01 = f2v{d2, d2} * f2v{b.rcp[0], b.rcp[1]};
+    const f2v f23 = f2v{d2, d2} * f2v{b.rcp[2], b.rcp[3]};
+    f[0] = f01.x;
+    f[1] = f01.y;
+    f[2] = f23.x;
+    f[3] = f23.y;
+}
+
 // Rd lookups of one record for the lane's 4 bands, accumulated:
 // acc[j] += Rd_j(d2) * e[j] (* w), as sampleProfile + the Mo() product (multipole.cpp:60-73;
 // diffusionutil.h:185,197) -- the same IEEE operations in the same order as the scalar code:
@@ -146,12 +170,7 @@ __host__ __device__ constexpr int near_row() {
 // The fetch half: f per band and the four pair loads (issued, not consumed).
 template <bool COUNT, int KLDS>
 __device__ __forceinline__ void band_rd_fetch(const BandLane &b, float d2, float f[4], RdPair v[4], int hist[kHist]) {
-    const f2v f01 = f2v{d2, d2} * f2v{b.rcp[0], b.rcp[1]};
-    const f2v f23 = f2v{d2, d2} * f2v{b.rcp[2], b.rcp[3]};
-    f[0] = f01.x;
-    f[1] = f01.y;
-    f[2] = f23.x;
-    f[3] = f23.y;
+    band_f(b, d2, f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t s = (uint32_t)f[j];  // saturating convert: f >= 2^32 -> 0xffffffff >= lm1
@@ -173,12 +192,7 @@ __device__ __forceinline__ void band_rd_fetch(const BandLane &b, float d2, float
 // -- the gather's binding resource -- never sees them. Same f, same pairs, so the same terms.
 template <int KLDS>
 __device__ __forceinline__ void band_rd_fetch_lds(const BandLane &b, float d2, float f[4], RdPair v[4]) {
-    const f2v f01 = f2v{d2, d2} * f2v{b.rcp[0], b.rcp[1]};
-    const f2v f23 = f2v{d2, d2} * f2v{b.rcp[2], b.rcp[3]};
-    f[0] = f01.x;
-    f[1] = f01.y;
-    f[2] = f23.x;
-    f[3] = f23.y;
+    band_f(b, d2, f);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const uint32_t s = (uint32_t)f[j];
@@ -231,8 +245,8 @@ __device__ __forceinline__ void band_rd_lerp(const float f[4], const RdPair v[4]
     }
 }
 
-// SampledSpectrum::FromRGB(rgb, SPECTRUM_REFLECTANCE) (spectrum.cpp:103-186; mo_kernel.hip
-// from_rgb_band restates its branches) for the group's four output bands. Its six cases only pick
+// SampledSpectrum::FromRGB(rgb, SPECTRUM_REFLECTANCE) (spectrum.cpp:103-186; spectrum_tables.h
+// refl_band restates its branches) for the group's four output bands. Its six cases only pick
 // which component is the minimum, middle and maximum, and two weight spectra by which component is
 // the minimum (X: Cyan, Magenta, Yellow) and the maximum (Y: Red, Green, Blue):
 //   out = .94 (W min + X (mid - min) + Y (max - mid)), clamped at 0.
@@ -379,16 +393,6 @@ __device__ __forceinline__ f2v lds_pair(const BandLane &b, uint32_t k) {
     return f2v{q[0], q[1]};
 }
 
-// the per-band indices d2 * rcp_j (multipole.cpp:63: the float product)
-__device__ __forceinline__ void band_f(const BandLane &b, float d2, float f[4]) {
-    const f2v f01 = f2v{d2, d2} * f2v{b.rcp[0], b.rcp[1]};
-    const f2v f23 = f2v{d2, d2} * f2v{b.rcp[2], b.rcp[3]};
-    f[0] = f01.x;
-    f[1] = f01.y;
-    f[2] = f23.x;
-    f[3] = f23.y;
-}
-
 template <bool COUNT>
 __device__ __forceinline__ void cg_count_rows(uint64_t addr, int hist[kHist]) {
     const int ns = wave_distinct(addr >> 5, addr >> 5), nl = wave_distinct(addr >> 7, addr >> 7);
@@ -410,6 +414,17 @@ __device__ __forceinline__ void cg_count_own(const uint64_t addr[4], int hist[kH
         hist[10] += nl;
         hist[12] += 1;
     }
+}
+
+// every band's exact pair from its LDS near-field row (a lane with s_j < klim_j for every band)
+__device__ __forceinline__ void cg_lds(const BandLane &b, const CgLane &c, float d2, CgRec &r) {
+    band_f(b, d2, r.f);
+    const f2v q0 = lds_pair(b, c.lrow[0] + (uint32_t)r.f[0]), q1 = lds_pair(b, c.lrow[1] + (uint32_t)r.f[1]);
+    const f2v q2 = lds_pair(b, c.lrow[2] + (uint32_t)r.f[2]), q3 = lds_pair(b, c.lrow[3] + (uint32_t)r.f[3]);
+    r.p01 = f4v{q0.x, q0.y, q1.x, q1.y};
+    r.p23 = f4v{q2.x, q2.y, q3.x, q3.y};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.f[j] = __builtin_amdgcn_fractf(r.f[j]);
 }
 
 // every band's exact pair from its own table (the u >= u1lim path, and cg_fix)
@@ -469,15 +484,7 @@ __device__ __forceinline__ CgRec cg_fetch(const BandLane &b, const CgLane &c, co
     const float v = __builtin_fminf(u, __builtin_fmaf(u, c.hinv, c.hc));
     uint32_t orow = 32u * ((uint32_t)v + c.rowoff);
     asm volatile("" : "+v"(orow));
-    if (p_lds) {  // s_j < klim_j for every band: inside its LDS row
-        band_f(b, d2, r.f);
-        const f2v q0 = lds_pair(b, c.lrow[0] + (uint32_t)r.f[0]), q1 = lds_pair(b, c.lrow[1] + (uint32_t)r.f[1]);
-        const f2v q2 = lds_pair(b, c.lrow[2] + (uint32_t)r.f[2]), q3 = lds_pair(b, c.lrow[3] + (uint32_t)r.f[3]);
-        r.p01 = f4v{q0.x, q0.y, q1.x, q1.y};
-        r.p23 = f4v{q2.x, q2.y, q3.x, q3.y};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) r.f[j] = __builtin_amdgcn_fractf(r.f[j]);
-    }
+    if (p_lds) cg_lds(b, c, d2, r);  // s_j < klim_j for every band: inside its LDS row
     // (keeps the LDS step ahead of the global ones: the compiler otherwise orders the three steps its
     // own way and puts the LDS step last)
     asm volatile("" : "+v"(r.p01), "+v"(r.p23)::"memory");
@@ -519,18 +526,7 @@ __device__ __forceinline__ void cg_fix2(const BandLane &b, const CgLane &c, cons
 // A record the caller has proven near for every lane (leaf_r2 < CommonGrid::lds_r2): LDS only.
 __device__ __forceinline__ CgRec cg_fetch_near(const BandLane &b, const CgLane &c, float d2) {
     CgRec r;
-    const f2v f01 = f2v{d2, d2} * f2v{b.rcp[0], b.rcp[1]};
-    const f2v f23 = f2v{d2, d2} * f2v{b.rcp[2], b.rcp[3]};
-    r.f[0] = f01.x;
-    r.f[1] = f01.y;
-    r.f[2] = f23.x;
-    r.f[3] = f23.y;
-    const f2v q0 = lds_pair(b, c.lrow[0] + (uint32_t)r.f[0]), q1 = lds_pair(b, c.lrow[1] + (uint32_t)r.f[1]);
-    const f2v q2 = lds_pair(b, c.lrow[2] + (uint32_t)r.f[2]), q3 = lds_pair(b, c.lrow[3] + (uint32_t)r.f[3]);
-    r.p01 = f4v{q0.x, q0.y, q1.x, q1.y};
-    r.p23 = f4v{q2.x, q2.y, q3.x, q3.y};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r.f[j] = __builtin_amdgcn_fractf(r.f[j]);
+    cg_lds(b, c, d2, r);
     return r;
 }
 
@@ -538,10 +534,9 @@ __device__ __forceinline__ CgRec cg_fetch_near(const BandLane &b, const CgLane &
 // gather's, the group rows' on the group grid. Its range test (multipole.cpp:65-66) is already in the
 // pairs: an LDS lane is never past a band's end, an own-table lane past it read the zero pair, and a row
 // cell within a step of a band's end is flagged (its lanes took the own path), past it the rows are 0.
-// e is E * area for a point (BandTree::band_ew) and Et for a node, w unused.
-template <bool POINT, bool RGB = false>
-__device__ __forceinline__ void cg_combine(const CgLane &c, const CgRec &r, float d2, const float e[4], float w,
-                                           f2v acc[2], lds_float *rk = nullptr) {
+// e is E * area for a point (BandTree::band_ew) and Et for a node.
+template <bool RGB = false>
+__device__ __forceinline__ void cg_combine(const CgRec &r, const float e[4], f2v acc[2], lds_float *rk = nullptr) {
     float rd[4];
     const RdPair v[4] = {{r.p01.x, r.p01.y}, {r.p01.z, r.p01.w}, {r.p23.x, r.p23.y}, {r.p23.z, r.p23.w}};
     // a + t (b - a), one rounding after the product: within an ulp or two of the reference's
@@ -555,11 +550,9 @@ __device__ __forceinline__ void cg_combine(const CgLane &c, const CgRec &r, floa
         asm("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(v[j].b), "v"(v[j].a));
         asm("v_fma_f32 %0, %1, %2, %3" : "=v"(rd[j]) : "v"(t), "v"(d), "v"(v[j].a));
     }
-    (void)d2;
     float o[4];
     if (RGB) from_rgb4_fused(rk, rd[0], rd[1], rd[2], o);  // slots 0..2: the R, G, B profiles on the grid
     const float *x = RGB ? o : rd;
-    (void)w;
 #pragma unroll
     for (int h = 0; h < 2; ++h)  // acc += Rd * (E area), one packed FMA per two bands
         acc[h] = __builtin_elementwise_fma(f2v{x[2 * h], x[2 * h + 1]}, f2v{e[2 * h], e[2 * h + 1]}, acc[h]);
@@ -692,7 +685,7 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                         const float4 et = et_g[nd];
                         const float e[4] = {et.x, et.y, et.z, et.w};
                         cg_fix<COUNT>(b, cl, a.table, d2, r, hist);
-                        cg_combine<false, RGB>(cl, r, d2, e, 1.f, acc, rk);
+                        cg_combine<RGB>(r, e, acc, rk);
                     } else {
                         const float4 et = et_g[node];
                         const float e[4] = {et.x, et.y, et.z, et.w};
@@ -724,8 +717,8 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                         const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
                         if (CG) {
                             const CgRec ra = cg_fetch_near(b, cl, d2a), rb = cg_fetch_near(b, cl, d2b);
-                            cg_combine<true, RGB>(cl, ra, d2a, e0, pa.w, lacc, rk);
-                            cg_combine<true, RGB>(cl, rb, d2b, e1, pb.w, lacc, rk);
+                            cg_combine<RGB>(ra, e0, lacc, rk);
+                            cg_combine<RGB>(rb, e1, lacc, rk);
                             continue;
                         }
                         float fa[4], fb[4];
@@ -758,8 +751,8 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                             CgRec rb = cg_fetch<COUNT>(b, cl, a.table, d2b, hist);
                             cg_fix2<COUNT>(b, cl, a.table, d2a, ra, d2b, rb, hist);
                             const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
-                            cg_combine<true, RGB>(cl, ra, d2a, e0, pa.w, lacc, rk);
-                            cg_combine<true, RGB>(cl, rb, d2b, e1, pb.w, lacc, rk);
+                            cg_combine<RGB>(ra, e0, lacc, rk);
+                            cg_combine<RGB>(rb, e1, lacc, rk);
                             continue;
                         }
                         float fa[4], fb[4];
@@ -790,7 +783,7 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                         const float4 ev = e_g[kq];
                         const float e[4] = {ev.x, ev.y, ev.z, ev.w};
                         cg_fix<COUNT>(b, cl, a.table, d2, r, hist);
-                        cg_combine<true, RGB>(cl, r, d2, e, ph.w, lacc, rk);
+                        cg_combine<RGB>(r, e, lacc, rk);
                     } else {
                         const float4 ev = e_g[kp];
                         const float e[4] = {ev.x, ev.y, ev.z, ev.w};
@@ -812,23 +805,6 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
     out[1] = acc[0].y;
     out[2] = acc[1].x;
     out[3] = acc[1].y;
-}
-
-// 30-bit Morton code of a point in [lo, lo + 1/inv) per axis (10 bits per axis, clamped).
-__device__ __forceinline__ uint32_t morton_expand10(uint32_t v) {
-    v &= 0x3ffu;
-    v = (v | (v << 16)) & 0x030000ffu;
-    v = (v | (v << 8)) & 0x0300f00fu;
-    v = (v | (v << 4)) & 0x030c30c3u;
-    v = (v | (v << 2)) & 0x09249249u;
-    return v;
-}
-__device__ __forceinline__ uint32_t morton30(float x, float y, float z, const float lo[3], const float inv[3]) {
-    const float q[3] = {(x - lo[0]) * inv[0], (y - lo[1]) * inv[1], (z - lo[2]) * inv[2]};
-    uint32_t c[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) c[k] = (uint32_t)fminf(fmaxf(q[k], 0.f), 1023.f);
-    return (morton_expand10(c[0]) << 2) | (morton_expand10(c[1]) << 1) | morton_expand10(c[2]);
 }
 #endif
 

@@ -1,5 +1,5 @@
 // mo_packet.h -- the packet traversal of the Mo() gather (device), shared by the Mo batch
-// kernel (mo_kernel.hip) and the render shading kernel (shade.hip).
+// kernel (mo_packet.hip) and the render shading kernel (shade.hip).
 //
 // One wave64 = a packet of 8 queries x 8 band-groups of 4 bands (lane = 8*g + k). The 8
 // queries walk the UNION of their pruned traversals of the pre-order octree once: node and

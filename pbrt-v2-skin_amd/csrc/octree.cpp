@@ -198,4 +198,29 @@ void build_octree(int npts, const float *p, const float *n, const float *E, cons
     f.emit(0, out.bmin, out.bmax, 0);
 }
 
+DeviceOrder device_order(const FlatOctree &t) {
+    DeviceOrder d;
+    d.hdr = t.hdr;
+    d.pt_hdr.resize(t.pt_hdr.size());
+    d.pt_e.resize(t.pt_e.size());
+    d.pt_index.resize(t.pt_index.size());
+    for (NodeHdr &h : d.hdr) {
+        h.pad = 0;
+        if (h.leaf_first < 0) continue;
+        int o = h.leaf_first;
+        for (int pass = 0; pass < 2; ++pass)
+            for (int i = 0; i < h.leaf_count; ++i) {
+                const size_t k = (size_t)h.leaf_first + i;
+                const bool blk = std::signbit(t.pt_hdr[4 * k + 3]);
+                if (blk != (pass == 1)) continue;
+                memcpy(&d.pt_hdr[4 * (size_t)o], &t.pt_hdr[4 * k], 4 * sizeof(float));
+                memcpy(&d.pt_e[(size_t)o * ROW], &t.pt_e[k * ROW], ROW * sizeof(float));
+                d.pt_index[o] = t.pt_index[k];
+                ++o;
+                if (pass == 0) ++h.pad;
+            }
+    }
+    return d;
+}
+
 }  // namespace mpss

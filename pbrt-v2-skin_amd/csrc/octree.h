@@ -42,4 +42,17 @@ struct FlatOctree {
 // p, n: npts*3; E: npts*NB; area: npts.  Throws Error on degenerate input.
 void build_octree(int npts, const float *p, const float *n, const float *E, const float *area, FlatOctree &out);
 
+// The point arrays and headers as the device holds them (DeviceOctree::upload): each leaf's black points
+// (E == 0: every kernel skips them, they add nothing) moved behind its other points, either kind keeping
+// its order, and the count of the others in NodeHdr::pad's low half (a leaf holds at most 8 points), so
+// the sharded gather's leaf loop needs no per-point test. pad's high half is 0 here (the device writes
+// its leaf code there, DeviceOctree::ensure_leaf_r2); nothing else in a header changes.
+struct DeviceOrder {
+    std::vector<NodeHdr> hdr;
+    std::vector<float> pt_hdr;      // M * 4
+    std::vector<float> pt_e;        // M * ROW
+    std::vector<int32_t> pt_index;  // M
+};
+DeviceOrder device_order(const FlatOctree &t);
+
 }  // namespace mpss

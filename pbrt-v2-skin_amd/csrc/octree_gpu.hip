@@ -15,13 +15,13 @@
 // InitHierarchy (diffusionutil.h:133-173) runs bottom-up one level per launch, one thread per node,
 // with the host build's float operations in the same order (children / points in slot order), and
 // the pre-order numbering top-down from the subtree sizes. Output: the DeviceOctree arrays
-// (mo_kernel.h), bit-identical to DeviceOctree::upload of the host build (tests/test_octree_gpu.py).
+// (device_octree.h), bit-identical to DeviceOctree::upload of the host build (tests/test_octree_gpu.py).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
 
-#include "mo_kernel.h"
+#include "device_octree.h"
 #include "spectral.h"
 
 namespace mpss {

@@ -31,6 +31,14 @@ void spectrum_from_sampled(const float *lambda, const float *vals, int n, float 
     }
 }
 
+const float *rgb_refl2spect(int t) {
+    static const float *const rows[7] = {MPSS_BAND_RGBREFL2SPECTWHITE,   MPSS_BAND_RGBREFL2SPECTCYAN,
+                                         MPSS_BAND_RGBREFL2SPECTMAGENTA, MPSS_BAND_RGBREFL2SPECTYELLOW,
+                                         MPSS_BAND_RGBREFL2SPECTRED,     MPSS_BAND_RGBREFL2SPECTGREEN,
+                                         MPSS_BAND_RGBREFL2SPECTBLUE};
+    return rows[t];
+}
+
 void spectrum_from_rgb(const float rgb[3], bool illum, float out[NB]) {
     const float *W = illum ? MPSS_BAND_RGBILLUM2SPECTWHITE : MPSS_BAND_RGBREFL2SPECTWHITE;
     const float *Cy = illum ? MPSS_BAND_RGBILLUM2SPECTCYAN : MPSS_BAND_RGBREFL2SPECTCYAN;

@@ -15,6 +15,9 @@ float average_spectrum_samples(const float *lambda, const float *vals, int n, fl
 void spectrum_from_sampled(const float *lambda, const float *vals, int n, float out[NB]);
 // SampledSpectrum::FromRGB, spectrum.cpp:103-187
 void spectrum_from_rgb(const float rgb[3], bool illuminant, float out[NB]);
+// FromRGB's reflectance tables by row: rgbRefl2Spect{White, Cyan, Magenta, Yellow, Red, Green, Blue}[t],
+// t < 7, NB floats each (the arrays of data/spectral_bands.h)
+const float *rgb_refl2spect(int t);
 
 // SampledSpectrum::y(), spectrum.h:387-393
 inline float spectrum_y(const float *s) {

@@ -91,7 +91,7 @@ def test_gpu_build_matches_oracle(mpss, oracle):
 
 
 def _leaf_code_bounds(nodes, max_error):
-    """ensure_leaf_r2's bound (mo_kernel.hip leaf_r2_kernel, in double) as the leaf code the gather
+    """ensure_leaf_r2's bound (device_octree.hip leaf_r2_kernel, in double) as the leaf code the gather
     compares: its float's high 16 bits rounded up -- with a 1e-6 margin either way for the device's
     double sqrt. Interior nodes and leaves without area: +inf (code 0x7f80)."""
     b0, b1 = nodes["bmin"].astype(np.float64), nodes["bmax"].astype(np.float64)
