@@ -371,6 +371,23 @@ int mpss_set_instrumentation(mpss_ctx *ctx, int kernel_timing, int count_travers
  * already on the device. The grids are the same bit for bit (mpss_get_common_grid against
  * mpss_host_common_grid). */
 int mpss_set_grid_builder(mpss_ctx *ctx, int on_host);
+/* The film's reconstruction filter, pbrt's PixelFilter (core/api.cpp MakeFilter, the units under filters/): weights from
+ * ImageFilm's 16 x 16 table, pixel ranges and table indices as ImageFilm::AddSample computes them
+ * (film/image.cpp:56-137). a, b: alpha of the gaussian; B, C of mitchell; tau of sinc; ignored otherwise. A
+ * new context has the box filter with widths 0.5 / 0.5, the only one whose weights are all 1: xyzw's W is
+ * then a sample count. Other filters (a box of another width included) collect samples from
+ * ceil(width + 0.5) pixels around a tile, out to the film's sample extent (GetSampleExtent), so pixels
+ * outside the frame are traced too; every tile renders its own halo, so tiles stay independent and a frame
+ * is the same bit for bit however it is cut. Hash sampler: a pixel inside the frame keeps the sampler key
+ * y * xres + x under every filter (the same camera samples, whatever the filter); a pixel (x, y) of the
+ * sample extent [xs, xe) x [ys, ye) outside the frame has the key xres * yres + (y - ys) * (xe - xs) +
+ * (x - xs). May be called between renders at any time; takes effect at the next mpss_render_tile(s).
+ * Widths <= 0, above 32 or not finite, non-finite parameters and unknown kinds: MPSS_ERR_INVALID. With
+ * sampler = MPSS_SAMPLER_REFERENCE only the default filter renders: mpss_render_tile(s) returns
+ * MPSS_ERR_INVALID under any other (the replay is laid out over the default filter's sample extent). */
+enum { MPSS_FILTER_BOX = 0, MPSS_FILTER_TRIANGLE = 1, MPSS_FILTER_GAUSSIAN = 2, MPSS_FILTER_MITCHELL = 3,
+       MPSS_FILTER_SINC = 4 };
+int mpss_set_pixel_filter(mpss_ctx *ctx, int kind, float xwidth, float ywidth, float a, float b);
 int mpss_reset_render_stats(mpss_ctx *ctx);
 
 /* ---- Monte-Carlo layered profile (renderer "mcprofile", src/renderers/mcprofile.cpp) ---- */

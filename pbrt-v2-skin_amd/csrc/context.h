@@ -12,6 +12,7 @@
 #include "material.h"
 #include "mo_kernel.h"
 #include "octree.h"
+#include "pixel_filter.h"
 #include "replay.h"
 #include "scene.h"
 #include "texture_build.h"
@@ -188,6 +189,11 @@ public:
         std::lock_guard<std::mutex> g(mu_);
         grid_on_host_ = on_host;
     }
+    // the film's reconstruction filter of later renders (mpss_set_pixel_filter); checked by the caller
+    void set_pixel_filter(const PixelFilter &f) {
+        std::lock_guard<std::mutex> g(mu_);
+        filter_ = f;
+    }
     void set_instrumentation(bool timing, int counting) {
         std::lock_guard<std::mutex> g(mu_);
         cfg_.kernel_timing = timing;
@@ -343,6 +349,7 @@ private:
     mpss_render_stats stats_{};
     DevBuf<unsigned long long> d_counts_;  // [kStatStride * kGroups] traversal counts (mo_kernel.h)
     mpss_config cfg_;
+    PixelFilter filter_;  // guarded by mu_; a render works on its own copy (TileCall)
     float max_error_, min_dist_;
     std::vector<std::unique_ptr<Material>> materials_;
 

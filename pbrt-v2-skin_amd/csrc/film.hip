@@ -3,8 +3,10 @@
 //                    NaN/negative/inf sample filter (samplerrenderer.cpp:119-133) and ToXYZ
 //   sky_kernel       the same for camera rays that escaped to infinite lights (samplerrenderer.cpp:144-151)
 //   film_kernel      ImageFilm::AddSample with the 0.5-wide box filter (film/image.cpp:77-137)
+//   film_filter_kernel  ... with any other filter, through ImageFilm's weight table (pixel_filter.h)
 #include "render.h"
 
+#include "film_filter.h"
 #include "geom.h"
 #include "light_sample.h"
 #include "spectrum_tables.h"
@@ -265,6 +267,93 @@ __global__ __launch_bounds__(256) void film_kernel(RenderScene sc, PieceList pl,
         }
     }
     float *o = out + ((size_t)(py - tb.y0) * out_stride_px + (px - tb.x0)) * 4;
+    o[0] = X;
+    o[1] = Y;
+    o[2] = Z;
+    o[3] = W;
+}
+
+// ImageFilm::AddSample (film/image.cpp:77-137) under any other filter, as a gather: no float atomics,
+// so a pixel's sums have one order -- the pixels of [py - ry, py + ry] x [px - rx, px + rx] row-major,
+// a pixel's samples in index order.
+// A workgroup owns a kFilmTile x kFilmTile block of the tile (a lane per pixel) and walks the block plus
+// its halo once: the workgroup stages the halo's camera samples in LDS -- image position minus 0.5
+// (recomputed from the hash: two words less to store and read back per sample than a float2 buffer
+// written by the camera pass) and XYZ, zeros for a sample without radiance, whose weight alone counts:
+// w * 0 added to a sum leaves its bits alone -- kFilmStage samples at a time, whole halo rows while
+// they fit (at 4 spp and a radius of 2 the whole 20 x 20 halo is one stage), parts of a row beyond.
+// Staging reads consecutive slots with consecutive lanes (a halo row's samples are contiguous), then
+// one 16-byte XYZ load per sample with radiance. Each lane then runs over its own window of the stage:
+// every staged sample is read by up to (2 rx + 1)(2 ry + 1) lanes, from LDS.
+// A lane's pixel lies in the frame, so AddSample's clamped range [Ceil(d - w), Floor(d + w)] holds px
+// exactly when d - w <= px <= d + w in float.
+__global__ __launch_bounds__(256) void film_filter_kernel(RenderScene sc, PieceList pl, SampleRecs rec, FilmFilter f) {
+    __shared__ float s_tab[kFilterTableSize * kFilterTableSize];
+    __shared__ float s_dx[kFilmStage], s_dy[kFilmStage], s_x[kFilmStage], s_y[kFilmStage], s_z[kFilmStage];
+    const int tid = (int)threadIdx.x;
+    const int k = piece_of(pl, (int)blockIdx.x);
+    const TileBatch &tb = pl.tb[k];
+    rec.slot += pl.off[k];
+    const int spp = tb.spp;
+    const int nbx = (tb.x1 - tb.x0 + kFilmTile - 1) / kFilmTile;
+    const int b = (int)blockIdx.x - pl.block0[k];
+    const int bx0 = tb.x0 + (b % nbx) * kFilmTile, by0 = tb.y0 + (b / nbx) * kFilmTile;
+    const int bx1 = min(bx0 + kFilmTile, tb.x1), by1 = min(by0 + kFilmTile, tb.y1);
+    // the block's halo, inside the piece's pixels
+    const int hx0 = max(bx0 - f.g.rx, tb.ex0), hx1 = min(bx1 + f.g.rx, tb.ex0 + tb.ew);
+    const int hy0 = max(by0 - f.g.ry, tb.ey0), hy1 = min(by1 + f.g.ry, tb.ey0 + tb.eh);
+    const int px = bx0 + (tid % kFilmTile), py = by0 + (tid / kFilmTile);
+    const bool own = px < bx1 && py < by1;
+    const float fpx = (float)px, fpy = (float)py;
+    s_tab[tid] = f.table[tid];
+    // this lane's window: halo rows [wy0, wy1), and samples [jlo, jhi) of a halo row
+    const int row_n = (hx1 - hx0) * spp;
+    const int wy0 = max(py - f.g.ry, hy0), wy1 = min(py + f.g.ry + 1, hy1);
+    const int jlo = (max(px - f.g.rx, hx0) - hx0) * spp, jhi = (min(px + f.g.rx + 1, hx1) - hx0) * spp;
+    const int rows = row_n <= kFilmStage ? kFilmStage / row_n : 1;
+    const int cols = row_n <= kFilmStage ? row_n : kFilmStage;
+    float X = 0.f, Y = 0.f, Z = 0.f, W = 0.f;
+    for (int r0 = hy0; r0 < hy1; r0 += rows) {
+        const int r1 = min(r0 + rows, hy1);
+        for (int j0 = 0; j0 < row_n; j0 += cols) {
+            const int j1 = min(j0 + cols, row_n), nj = j1 - j0;
+            __syncthreads();  // the table is written; the stage before this one is read
+            const int n = (r1 - r0) * nj;  // <= kFilmStage
+            for (int i = tid; i < n; i += 256) {
+                const int qy = r0 + i / nj, j = j0 + i % nj;
+                const int qx = hx0 + j / spp, s = j % spp;
+                float sx, sy;
+                image_sample_keyed(tb.seed, filter_pixel_key(f.g, sc.xres, sc.yres, qx, qy), qx, qy, s, sx, sy);
+                const int32_t v = rec.slot[((int64_t)(qy - tb.ey0) * tb.ew + (qx - tb.ex0)) * spp + s];
+                float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (v >= 0) x = rec.xyz[v];
+                s_dx[i] = sx - 0.5f;
+                s_dy[i] = sy - 0.5f;
+                s_x[i] = x.x;
+                s_y[i] = x.y;
+                s_z[i] = x.z;
+            }
+            __syncthreads();
+            if (!own) continue;
+            const int ja = max(j0, jlo), jb = min(j1, jhi);
+            for (int qy = max(r0, wy0); qy < min(r1, wy1); ++qy) {
+                const int base = (qy - r0) * nj - j0;
+                for (int j = ja; j < jb; ++j) {
+                    const int i = base + j;
+                    const float dx = s_dx[i], dy = s_dy[i];
+                    if (!(dx - f.g.wx <= fpx && dx + f.g.wx >= fpx && dy - f.g.wy <= fpy && dy + f.g.wy >= fpy)) continue;
+                    const float w = s_tab[filter_index(py, dy, f.g.inv_wy) * kFilterTableSize +
+                                          filter_index(px, dx, f.g.inv_wx)];
+                    X += w * s_x[i];
+                    Y += w * s_y[i];
+                    Z += w * s_z[i];
+                    W += w;
+                }
+            }
+        }
+    }
+    if (!own) return;
+    float *o = pl.out[k] + ((size_t)(py - tb.y0) * pl.out_stride[k] + (px - tb.x0)) * 4;
     o[0] = X;
     o[1] = Y;
     o[2] = Z;

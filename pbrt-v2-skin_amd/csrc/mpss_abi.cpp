@@ -451,6 +451,20 @@ int mpss_set_grid_builder(mpss_ctx *c, int on_host) {
     });
 }
 
+int mpss_set_pixel_filter(mpss_ctx *c, int kind, float xwidth, float ywidth, float a, float b) {
+    return guarded([&] {
+        PixelFilter f;
+        f.kind = kind;
+        f.xwidth = xwidth;
+        f.ywidth = ywidth;
+        f.a = a;
+        f.b = b;
+        if (const char *why = filter_invalid(f)) throw Error(MPSS_ERR_INVALID, std::string("mpss_set_pixel_filter: ") + why);
+        require(c, "mpss_set_pixel_filter: null ctx");
+        reinterpret_cast<Context *>(c)->set_pixel_filter(f);
+    });
+}
+
 int mpss_reset_render_stats(mpss_ctx *c) {
     return guarded([&] {
         require(c, "mpss_reset_render_stats: null ctx");

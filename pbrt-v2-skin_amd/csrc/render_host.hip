@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "context.h"
+#include "film_filter.h"
 #include "render.h"
 
 namespace mpss {
@@ -110,6 +111,10 @@ struct Context::TileCall {
     std::vector<SssMat> sss;
     float max_error;
     GatherOpts gopts;
+    // a non-default pixel filter (pixel_filter.h): the *_filter_kernel instances run, over pieces that
+    // reach `ff.g.rx, ry` pixels beyond their tiles
+    bool filtered;
+    FilmFilter ff;
     std::vector<Timed> timed;
     // (the per-hit pointers are valid after batch_reserve_hits)
     SampleRecs recs() const {
@@ -148,7 +153,7 @@ void Context::batch_window(TileCall &c, RenderScene &sc, const PlanBatch &b) {
 // the batch's pieces, kMaxPieces per launch, through primary_kernel or film_kernel
 void Context::launch_pieces(const TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b,
                             bool film) {
-    for (const LaunchGroup &g : launch_groups(plan, b, film)) {
+    for (const LaunchGroup &g : launch_groups(plan, b, film, c.filtered ? kFilmTile : 0)) {
         PieceList pl{};
         pl.n = g.n;
         for (int j = 0; j < g.n; ++j) {
@@ -160,8 +165,14 @@ void Context::launch_pieces(const TileCall &c, const RenderScene &sc, const Tile
             pl.out_stride[j] = g.out_stride[j];
         }
         pl.block0[g.n] = g.blocks;
-        if (film)
+        if (film && c.filtered)
+            hipLaunchKernelGGL(film_filter_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs(),
+                               c.ff);
+        else if (film)
             hipLaunchKernelGGL(film_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs());
+        else if (c.filtered)
+            hipLaunchKernelGGL(primary_filter_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs(),
+                               c.ff.g);
         else
             hipLaunchKernelGGL(primary_kernel, dim3((unsigned)g.blocks), dim3(256), 0, c.stream, sc, pl, c.recs());
     }
@@ -215,7 +226,11 @@ void Context::batch_direct(TileCall &c, const RenderScene &sc, int64_t nh) {
     hipEvent_t ev{};
     if (sc.any_tex) {
         time_begin(c.timing, stream, ev);
-        hipLaunchKernelGGL(shade_tex_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh);
+        if (c.filtered)
+            hipLaunchKernelGGL(shade_tex_filter_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh,
+                               c.ff.g);
+        else
+            hipLaunchKernelGGL(shade_tex_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh);
         time_end(c.timing, stream, ev, 5, c.timed);
     }
     time_begin(c.timing, stream, ev);
@@ -247,7 +262,7 @@ void Context::batch_mo(TileCall &c, int64_t nh) {
     time_end(c.timing, c.stream, ev, 2, c.timed);
 }
 
-// Li assembly per hit, the sky behind the misses, then the box-filtered film per piece
+// Li assembly per hit, the sky behind the misses, then the filtered film per piece
 void Context::batch_film(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, int64_t nh) {
     const SampleRecs rec = c.recs();
     const dim3 per_hit((unsigned)((nh + 255) / 256));
@@ -261,8 +276,8 @@ void Context::batch_film(TileCall &c, const RenderScene &sc, const TilePlan &pla
 }
 
 // SamplerRenderer::Render restricted to pixel rectangles. plan_tiles (tile_plan.h) cuts each rectangle
-// into row pieces (a piece = the rows plus a one-pixel border of samples that the box filter carries
-// in) and packs the pieces into batches of <= max_batch_samples camera samples. Per batch:
+// into row pieces (a piece = the rows plus the border of samples that the pixel filter carries in: one
+// pixel for the default box, the filter's halo otherwise) and packs the pieces into batches of <= max_batch_samples camera samples. Per batch:
 // camera kernel over the pieces (all pieces append their surface hits to one compacted list) -> direct
 // lighting per hit -> ONE sharded Mo() gather per BSSRDF material over the batch's hits -> film kernel
 // over the pieces. Calls on different streams may overlap: each takes its own workspace (RenderWorkspace),
@@ -282,6 +297,10 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
         if (spp > kReplayMaxSpp)
             throw Error(MPSS_ERR_INVALID, "render_tile: spp must be at most 4096 for the replay sampler");
         check_replay_lds(spp, "render_tile");
+        // the replay's windows and pbrt's task split are laid out over the default filter's sample extent
+        if (!filter_.is_default())
+            throw Error(MPSS_ERR_INVALID, "render_tile: the reference sampler renders only with the default pixel "
+                                          "filter (box 0.5 / 0.5); set that filter or use the hash sampler");
     }
     for (int i = 0; i < n; ++i) {
         if (!tile_rect_ok(rects + 4 * i, W, H)) throw Error(MPSS_ERR_INVALID, "render_tile: bad rectangle");
@@ -292,6 +311,9 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
     c.outs = outs;
     c.spp = spp;
     c.seed = seed;
+    c.filtered = !filter_.is_default();
+    if (c.filtered) c.ff = film_filter(filter_, W, H);
+    const PlanHalo halo = filter_plan_halo(filter_, W, H);
     if (have_octree_)
         for (size_t i = 0; i < materials_.size(); ++i)
             if (!materials_[i]->dipole && !materials_[i]->no_bssrdf)
@@ -322,7 +344,7 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
     lk.unlock();
     InflightGuard guard{this, ws, stream};  // every way out: workspace back to the pool, inflight_ down
 
-    const TilePlan plan = plan_tiles(W, H, spp, seed, n, rects, max_batch, replay, replay_k, kReplayWindowFloats);
+    const TilePlan plan = plan_tiles(W, H, spp, seed, n, rects, max_batch, replay, replay_k, kReplayWindowFloats, halo);
     int64_t n_samples = 0, n_sss = 0;
     if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));
     for (const PlanBatch &b : plan.batches) {

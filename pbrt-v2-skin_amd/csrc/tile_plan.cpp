@@ -11,6 +11,11 @@ bool tile_rect_ok(const int32_t *r, int W, int H) {
 
 TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *rects, int64_t max_batch,
                     bool replay, int replay_k, int64_t window_limit) {
+    return plan_tiles(W, H, spp, seed, n, rects, max_batch, replay, replay_k, window_limit, PlanHalo{1, 1, 0, W, 0, H});
+}
+
+TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *rects, int64_t max_batch,
+                    bool replay, int replay_k, int64_t window_limit, const PlanHalo &halo) {
     TilePlan plan;
     std::vector<PlanPiece> &pieces = plan.pieces;
     // replay: rectangles in row order, so that consecutive batches continue the task streams
@@ -26,9 +31,9 @@ TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *
     for (int i : order) {
         const int x0 = rects[4 * i], x1 = rects[4 * i + 1], y0 = rects[4 * i + 2], y1 = rects[4 * i + 3];
         const int tw = x1 - x0;
-        const int ex0 = std::max(x0 - 1, 0);
-        const int ew = std::min(x1 + 1, W) - ex0;
-        const int rows = (int)std::max<int64_t>(1, max_batch / ((int64_t)ew * spp) - 2);
+        const int ex0 = std::max(x0 - halo.rx, halo.xs);
+        const int ew = std::min(x1 + halo.rx, halo.xe) - ex0;
+        const int rows = (int)std::max<int64_t>(1, max_batch / ((int64_t)ew * spp) - 2 * halo.ry);
         for (int yb = y0; yb < y1; yb += rows) {
             const int ye = std::min(y1, yb + rows);
             PlanPiece p;
@@ -37,9 +42,9 @@ TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *
             p.tb.y0 = yb;
             p.tb.y1 = ye;
             p.tb.ex0 = ex0;
-            p.tb.ey0 = std::max(yb - 1, 0);
+            p.tb.ey0 = std::max(yb - halo.ry, halo.ys);
             p.tb.ew = ew;
-            p.tb.eh = std::min(ye + 1, H) - p.tb.ey0;
+            p.tb.eh = std::min(ye + halo.ry, halo.ye) - p.tb.ey0;
             p.tb.spp = spp;
             p.tb.seed = seed;
             p.tb.nsamples = (int64_t)p.tb.ew * p.tb.eh * spp;
@@ -102,7 +107,7 @@ TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *
     return plan;
 }
 
-std::vector<LaunchGroup> launch_groups(const TilePlan &plan, const PlanBatch &b, bool film) {
+std::vector<LaunchGroup> launch_groups(const TilePlan &plan, const PlanBatch &b, bool film, int film_tile) {
     std::vector<LaunchGroup> groups;
     int64_t off = 0;
     for (size_t k0 = b.first; k0 < b.end; k0 += kMaxPieces) {
@@ -117,7 +122,10 @@ std::vector<LaunchGroup> launch_groups(const TilePlan &plan, const PlanBatch &b,
             g.block0[j] = blocks;
             g.off[j] = off;
             g.out_stride[j] = tw;
-            blocks += (int)((items + 255) / 256);
+            if (film && film_tile > 0)
+                blocks += ((tw + film_tile - 1) / film_tile) * ((tb.y1 - tb.y0 + film_tile - 1) / film_tile);
+            else
+                blocks += (int)((items + 255) / 256);
             off += tb.nsamples;
         }
         g.block0[g.n] = g.blocks = blocks;

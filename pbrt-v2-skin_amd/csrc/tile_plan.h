@@ -10,7 +10,9 @@ namespace mpss {
 
 // A tile [x0,x1) x [y0,y1) extended by one pixel on every side that exists (origin ex0, ey0;
 // ew x eh pixels): a sample whose float image coordinate rounds onto a pixel edge also lands
-// in the neighbouring pixel (film_kernel). A kernel argument (render.h PieceList).
+// in the neighbouring pixel (film_kernel). Under a non-default pixel filter the extension is the
+// filter's halo inside the film's sample extent (PlanHalo below), and ex0, ey0 may be negative.
+// A kernel argument (render.h PieceList).
 struct TileBatch {
     int x0, x1, y0, y1, ex0, ey0, ew, eh, spp;
     uint32_t seed;
@@ -66,8 +68,19 @@ bool tile_rect_ok(const int32_t *r, int W, int H);
 TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *rects, int64_t max_batch,
                     bool replay, int replay_k, int64_t window_limit);
 
+// How far a piece reaches beyond its tile: (rx, ry) pixels (a filter's halo radius, pixel_filter.h),
+// clipped to [xs, xe) x [ys, ye). The default filter: one pixel, clipped to the frame -- what the
+// overload above plans with. Another filter: its halo, clipped to the film's sample extent, so pieces at
+// the image edge hold out-of-frame pixels (ex0 / ey0 < 0, ex0 + ew > W).
+struct PlanHalo {
+    int rx, ry, xs, xe, ys, ye;
+};
+TilePlan plan_tiles(int W, int H, int spp, uint32_t seed, int n, const int32_t *rects, int64_t max_batch,
+                    bool replay, int replay_k, int64_t window_limit, const PlanHalo &halo);
+
 // The launches of batch b; blocks per piece: ceil(items / 256) of its samples (primary_kernel) or, for
-// film, its tile pixels (film_kernel).
-std::vector<LaunchGroup> launch_groups(const TilePlan &plan, const PlanBatch &b, bool film);
+// film, its tile pixels (film_kernel); film_tile > 0: one block per film_tile x film_tile pixels of the tile
+// (film_filter_kernel).
+std::vector<LaunchGroup> launch_groups(const TilePlan &plan, const PlanBatch &b, bool film, int film_tile = 0);
 
 }  // namespace mpss

@@ -111,6 +111,7 @@ _sig("mpss_update_layeredskin", C.c_int, [vp, u32, C.POINTER(LayeredSkin)])
 _sig("mpss_build_counts", C.c_int, [vp, C.POINTER(C.c_uint64)])
 _sig("mpss_get_common_grid", C.c_int, [vp, u32, C.c_int, vp, u32p] + [vp] * 11 + [C.POINTER(C.c_int)])
 _sig("mpss_set_grid_builder", C.c_int, [vp, C.c_int])
+_sig("mpss_set_pixel_filter", C.c_int, [vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float])
 _sig("mpss_set_material_tables", C.c_int, [vp, f32p, u32, f32p, f32p, u32, vp, C.c_int, u32p])
 _sig("mpss_add_dipole_material", C.c_int, [vp, f32p, f32p, C.c_float, u32p])
 _sig("mpss_host_dipole_rd", C.c_int, [f32p, f32p, C.c_float, u32, vp, vp, vp])
@@ -526,6 +527,31 @@ def host_sog_solve(a, b, quirk=True):
 
 
 # ------------------------------------------------------------------ device context
+# pbrt's PixelFilter names in MPSS_FILTER_* order, and per kind (default width, ((parameter, default), ...))
+# as core/api.cpp MakeFilter's Create*Filter read them
+PIXEL_FILTERS = ("box", "triangle", "gaussian", "mitchell", "sinc")
+_FILTER_DEFAULTS = ((0.5, ()), (2.0, ()), (2.0, (("alpha", 2.0),)), (2.0, (("B", 1.0 / 3.0), ("C", 1.0 / 3.0))),
+                    (4.0, (("tau", 3.0),)))
+
+
+def pixel_filter(kind, xwidth=None, ywidth=None, **params):
+    """(kind, xwidth, ywidth, a, b) as mpss_set_pixel_filter takes them, the reference's defaults filled
+    in. An unknown kind or a parameter the kind does not have raises ValueError."""
+    if isinstance(kind, str):
+        if kind not in PIXEL_FILTERS:
+            raise ValueError("unknown pixel filter %r" % kind)
+        kind = PIXEL_FILTERS.index(kind)
+    kind = int(kind)
+    if not 0 <= kind < len(PIXEL_FILTERS):
+        raise ValueError("unknown pixel filter kind %d" % kind)
+    width, names = _FILTER_DEFAULTS[kind]
+    extra = set(params) - {n for n, _ in names}
+    if extra:
+        raise ValueError("pixel filter %r has no parameter %s" % (PIXEL_FILTERS[kind], ", ".join(sorted(extra))))
+    ab = [float(params.get(n, d)) for n, d in names] + [0.0, 0.0]
+    return (kind, float(width if xwidth is None else xwidth), float(width if ywidth is None else ywidth), ab[0], ab[1])
+
+
 class Context:
     """One MultipoleSubsurfaceIntegrator instance (multipolesubsurface.h:36-80) on one GPU."""
 
@@ -565,6 +591,12 @@ class Context:
         """mpss_set_grid_builder: the common grids' per-knot scan of later material builds on the host
         (True) or on the GPU (False); the same grids either way."""
         check(_lib.mpss_set_grid_builder(self.h, int(bool(on_host))))
+
+    def set_pixel_filter(self, kind, xwidth=None, ywidth=None, **params):
+        """mpss_set_pixel_filter: the film's reconstruction filter of later renders. kind: a name of
+        PIXEL_FILTERS or its MPSS_FILTER_* value; widths default to the reference's for the kind;
+        params: alpha (gaussian), B and C (mitchell), tau (sinc), the reference's defaults when left out."""
+        check(_lib.mpss_set_pixel_filter(self.h, *pixel_filter(kind, xwidth, ywidth, **params)))
 
     def common_grid(self, mid, near_field=5088):
         """mpss_get_common_grid: the grid the context built for material `mid` and the LDS layout

@@ -159,6 +159,8 @@ class Scene:
         self.materials = []  # list of layeredskin param dicts
         self.meshes = []     # dicts: P (world), N, S, uv, indices, o2w, w2o, reverse, material
         self.lights = []     # dicts: center, radius, L (rgb), nsamples; or kind="infinite", L, scale, l2w, w2l
+        # (kind, xwidth, ywidth, a, b) of mpss.pixel_filter: PixelFilter, the default "box" 0.5 / 0.5
+        self.pixel_filter = (0, 0.5, 0.5, 0.0, 0.0)
         self.base_dir = "."
         self.renderer = None  # ("mcprofile" or "batchmcprofile", ParamSet) for the MC profile renderers;
         #                       ("multipoleprofilefit", description dict) for the profile fit (tools/profilefit.py)
@@ -171,6 +173,7 @@ _SKIN_FLOATS = ("roughness", "nmperunit", "f_mel", "f_eu", "f_blood", "f_ohg", "
 
 
 def load(path, **override):
+    import mpss
     sc = Scene()
     base = os.path.dirname(os.path.abspath(path))
     ctm = np.eye(4)
@@ -252,9 +255,12 @@ def load(path, **override):
                         raise ValueError("Renderer %r is outside this path" % cls)
                     else:
                         sc.renderer = (cls, ps) if cls != "sampler" else None
-                elif d in ("PixelFilter",):
-                    if cls != "box" or ps.one("xwidth", 0.5) != 0.5 or ps.one("ywidth", 0.5) != 0.5:
-                        raise ValueError("only the default 0.5-wide box filter is supported")
+                elif d == "PixelFilter":
+                    if cls not in mpss.PIXEL_FILTERS:
+                        raise ValueError("PixelFilter %r is unknown" % cls)
+                    names = {"gaussian": ("alpha",), "mitchell": ("B", "C"), "sinc": ("tau",)}.get(cls, ())
+                    sc.pixel_filter = mpss.pixel_filter(cls, ps.one("xwidth"), ps.one("ywidth"),
+                                                        **{k: ps.one(k) for k in names if ps.one(k) is not None})
                 elif d == "Texture":
                     textures[name] = _texture(cls, _kind, ps, base)
                 elif d == "Material":
@@ -556,6 +562,9 @@ def build_context(sc, timings=None, grid_on_host=None, **cfg_kw):
             ctx.add_sphere_light(li["center"], li["radius"], mpss.host_from_rgb(li["L"]), li["nsamples"])
     r2c, c2w = sc.raster_to_camera()
     ctx.set_camera(r2c, c2w, sc.xres, sc.yres)
+    kind, xw, yw, a, b = sc.pixel_filter
+    if (kind, xw, yw) != (0, 0.5, 0.5):  # (a new context has the default)
+        ctx.set_pixel_filter(kind, xw, yw, **dict(zip([n for n, _ in mpss._FILTER_DEFAULTS[kind][1]], (a, b))))
     pf = sc.integrator.get("pointsfile")
     if pf:  # MultipoleSubsurfaceIntegrator reads the points instead of tessellating
         ctx.load_pointsfile(pf if os.path.isabs(pf) else os.path.join(sc.base_dir, pf))
