@@ -268,6 +268,20 @@ int mpss_octree_export(mpss_ctx *ctx, void *nodes, float *node_et, float *pt_hdr
 int mpss_mo_batch(mpss_ctx *ctx, uint32_t material_id, uint32_t q, const float *p_dev, float *mo_dev,
                   int32_t *counters_dev, void *stream);
 
+/* mpss_mo_batch through the sharded gather's instrumented pass (exact_mo 0 and a tabulated profile; else
+ * MPSS_ERR_INVALID), with its statistics: stats (host) receives MPSS_MO_PATH_GROUPS x MPSS_MO_PATH_STATS
+ * counts, per band group: 0 node visits, 1 point visits (summed over queries), 2 / 3 wave node / point
+ * iterations, 4..7 table lookups inside the profile (all, and at entries < 4096, 8192, 16384); with the common
+ * grid: 8 / 9 / 10 lane-records read from the group rows / the LDS near field / the bands' own tables,
+ * 11..16 the L2 footprint of the row and own-table fetches, 17 lane-records of flagged row cells; 18 / 19
+ * lane-opens of leaves that qualify for the LDS-only pair loop / that hold an odd live count; 20 / 21 / 22
+ * lane-visits pruned by the reach test / of black nodes / inside the box of a node other than the root.
+ * Synchronous, on the null stream. */
+#define MPSS_MO_PATH_GROUPS 8
+#define MPSS_MO_PATH_STATS 23
+int mpss_mo_batch_paths(mpss_ctx *ctx, uint32_t material_id, uint32_t q, const float *p_dev, float *mo_dev,
+                        uint64_t *stats);
+
 /* ---- scene slice of the per-pixel path (the renderer feeds pbrt's parsed scene through these) ---- */
 /* TriangleMesh (shapes/trianglemesh.cpp:43-73): P already in world space (the ctor's ObjectToWorld),
  * N / S in object space (nullable), uv (nullable), o2w / w2o = ObjectToWorld and its inverse

@@ -113,7 +113,7 @@ void Context::ensure_layouts() {
 // layout are read-only here; the chunk counters of the sharded gather come from a pooled
 // workspace, so concurrent calls on different streams share nothing they write.
 void Context::mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, int32_t *counters_dev,
-                       hipStream_t stream) {
+                       hipStream_t stream, unsigned long long *counts_dev) {
     activate();
     RenderWorkspace *ws = nullptr;
     const BandLayout *layout = nullptr;
@@ -140,6 +140,8 @@ void Context::mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, 
         ++inflight_;  // until the kernels are queued (an octree rebuild waits for it)
     }
     InflightGuard guard{this, ws, stream};
+    if (counts_dev && mode != 0)
+        throw Error(MPSS_ERR_INVALID, "path statistics come from the sharded gather only (exact_mo 0, a tabulated profile)");
     if (mode == -1) {
         launch_mo_dipole(dev_octree_, m->dev_dipole.ptr, max_error_, q, p_dev, out_dev, NB, counters_dev, stream);
         return;
@@ -156,8 +158,22 @@ void Context::mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, 
         if (ws->pending) MPSS_HIP(hipStreamWaitEvent(stream, ws->done, 0));
     }
     launch_mo_gather(dev_octree_, layout, m->dev_profile, max_error_, q, p_dev, out_dev, NB, counters_dev,
-                     ws ? ws->work.ptr : nullptr, perm, mode, opts, stream);
+                     ws ? ws->work.ptr : nullptr, perm, mode, opts, stream, counts_dev);
     guard.release();
+}
+
+// mpss_mo_batch_paths: the instrumented pass of the sharded gather over a batch, its per-group
+// statistics (mo_kernel.h kStatStride) copied to the host. Synchronous, on the null stream.
+void Context::mo_batch_paths(uint32_t mid, int q, const float *p_dev, float *out_dev, uint64_t *stats) {
+    activate();
+    const size_t n = (size_t)kStatStride * kGroups;
+    DevBuf<unsigned long long> d;
+    d.alloc(n);
+    MPSS_HIP(hipMemset(d.ptr, 0, n * sizeof(unsigned long long)));
+    mo_batch(mid, q, p_dev, out_dev, nullptr, nullptr, d.ptr);
+    MPSS_HIP(hipStreamSynchronize(nullptr));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the statistics are 64-bit counts");
+    MPSS_HIP(hipMemcpy(stats, d.ptr, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
 }
 
 void Context::activate() const { MPSS_HIP(hipSetDevice(cfg_.device)); }

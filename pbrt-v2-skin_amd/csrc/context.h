@@ -162,7 +162,10 @@ public:
     void check_replay_lds(int spp, const char *who) const;  // replay_check_lds over the scene's lights
     // SubsurfaceOctreeNode::Mo over q device-resident points with material `mid`'s profile
     // (mpss_mo_batch); stream-ordered, safe for concurrent callers on their own streams
-    void mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, int32_t *counters_dev, hipStream_t stream);
+    void mo_batch(uint32_t mid, int q, const float *p_dev, float *out_dev, int32_t *counters_dev, hipStream_t stream,
+                  unsigned long long *counts_dev = nullptr);
+    // the sharded gather's instrumented pass over a batch: stats[kGroups][kStatStride] (mo_kernel.h), synchronous
+    void mo_batch_paths(uint32_t mid, int q, const float *p_dev, float *out_dev, uint64_t *stats);
     // Cost probe for tile dealing: one camera ray through every pixel centre; per rect, the rays
     // that hit a BSSRDF surface (sss) and any mesh surface (surf). Synchronous.
     void tile_costs(int n, const int32_t *rects, int64_t *sss, int64_t *surf);

@@ -45,8 +45,13 @@ namespace mpss {
 // common grid only: 4..6 lane-records by path (group rows, LDS near field, the bands' own tables);
 // 7..8 distinct 32-byte sectors and 9..10 distinct 128-byte lines the path's loads touch, summed
 // over wave fetches (rows, own tables: what the vector-memory path asks of L2); 11..12 wave fetches
-// with a lane on the path (rows, own tables).
-constexpr int kHist = 13;
+// with a lane on the path (rows, own tables); 13 lane-records whose group row was flagged and re-read
+// from the bands' own tables (cg_fix); per lane and leaf: 14 opened leaves that qualify for the LDS-only
+// pair loop (leaf code under the group's limit, two live points or more -- the loop itself runs in the
+// uninstrumented kernel only), 15 opened leaves with an odd live count; per lane and node: 16 visits
+// pruned by the reach test, 17 visits of a black node, 18 visits inside the box of a node other than
+// the root that passed the reach test.
+constexpr int kHist = 19;
 
 // (kGroups, BandGroups and CommonGrid -- the grid the far lookups read -- are plain types shared with the
 // host-only grid builder: common_grid_types.h)
@@ -511,12 +516,14 @@ template <bool COUNT>
 __device__ __forceinline__ void cg_fix(const BandLane &b, const CgLane &c, const float *table, float d2, CgRec &r,
                                        int hist[kHist]) {
     const bool bad = r.p01.x != r.p01.x;
+    if (COUNT && bad) ++hist[13];
     if (__builtin_amdgcn_ballot_w64(bad) != 0 && bad) cg_own<COUNT>(b, c, table, d2, r, hist);
 }
 template <bool COUNT>
 __device__ __forceinline__ void cg_fix2(const BandLane &b, const CgLane &c, const float *table, float d2a,
                                         CgRec &ra, float d2b, CgRec &rb, int hist[kHist]) {
     const bool bad_a = ra.p01.x != ra.p01.x, bad_b = rb.p01.x != rb.p01.x;
+    if (COUNT) hist[13] += (int)bad_a + (int)bad_b;
     if (__builtin_amdgcn_ballot_w64(bad_a || bad_b) != 0) {
         if (bad_a) cg_own<COUNT>(b, c, table, d2a, ra, hist);
         if (bad_b) cg_own<COUNT>(b, c, table, d2b, rb, hist);
@@ -573,12 +580,14 @@ __device__ __forceinline__ void band_rd_accumulate(const BandLane &b, float d2, 
 // a multiply's rate: the multiplies measured 0.7 % faster once the gather was VALU-bound,
 // profiles/r06_grid_ab.txt r06n). The rare near-ties (and NaN / inf) take the exact division, so the
 // decision is always that of fl(sum_area / d2) < max_error (diffusionutil.h:182).
-__device__ __forceinline__ bool dw_below(float a, float d, float m, float m_lo, float m_hi) {
-    // (the masks as ballots: two compares, the rest scalar mask logic)
-    const uint64_t m_below = __builtin_amdgcn_ballot_w64(a < d * m_lo);
-    const uint64_t m_above = __builtin_amdgcn_ballot_w64(a > d * m_hi);
-    bool below = __builtin_amdgcn_inverse_ballot_w64(m_below);
-    if (__builtin_amdgcn_inverse_ballot_w64(~(m_below | m_above))) below = (a / d) < m;
+__device__ __forceinline__ uint64_t dw_below(float a, float d, float m, float m_lo, float m_hi, uint64_t lanes) {
+    // (the decision as a lane mask: two compares, the rest scalar mask logic. Only the bits of `lanes`
+    // mean anything -- a lane outside it may come back set or clear, whatever its a and d hold -- so
+    // the caller ANDs the result with its own mask; `lanes` keeps such lanes from raising a tie)
+    uint64_t below = __builtin_amdgcn_ballot_w64(a < d * m_lo);
+    const uint64_t above = __builtin_amdgcn_ballot_w64(a > d * m_hi);
+    const uint64_t tie = lanes & ~(below | above);
+    if (tie != 0) below |= tie & __builtin_amdgcn_ballot_w64((a / d) < m);
     return below;
 }
 
@@ -658,51 +667,68 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                      "s"(h.bminz), "s"(h.bmaxx), "s"(h.bmaxy), "s"(h.bmaxz), "s"(h.skip), "s"(h.leaf_first),
                      "s"(h.flags), "s"(h.pad), "s"(h.leaf_count), "s"(h.depth));
         const int skip = h.skip;
-        bool open = false;
-        if (node >= resume) {
-            if (COUNT) ++k_nodes;
-            // distance from p to the node box per axis (0 inside the slab)
-            const float bx = fmaxf(fmaxf(h.bminx - px, px - h.bmaxx), 0.f);
-            const float by = fmaxf(fmaxf(h.bminy - py, py - h.bmaxy), 0.f);
-            const float bz = fmaxf(fmaxf(h.bminz - pz, pz - h.bmaxz), 0.f);
-            // exact-zero pruning with a 1e-4 margin (prune_f), so the test may round freely
-            const float box2 = __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx));
-            if (box2 >= box_lim || (h.flags & NODE_BLACK)) {
-                resume = skip;
-            } else {
-                const float dx = px - h.px, dy = py - h.py, dz = pz - h.pz;
-                const float d2 = dx * dx + dy * dy + dz * dz;
-                // nodeBound.Inside(p) <=> every per-axis distance is 0 (the subtractions' signs are exact)
-                const bool inside = fmaxf(fmaxf(bx, by), bz) == 0.f;
-                if (dw_below(h.sum_area, d2, a.max_error, m_lo, m_hi) && !inside) {
-                    resume = skip;
-                    if (CG) {
-                        CgRec r = cg_fetch<COUNT>(b, cl, a.table, d2, hist);
-                        // Et's scalar load issued behind the record's table loads: issued before them,
-                        // the wait for the LDS step's reads (lgkmcnt) would wait for it too
-                        int nd = node;
-                        asm volatile("" : "+s"(nd)::"memory");
-                        const float4 et = et_g[nd];
-                        const float e[4] = {et.x, et.y, et.z, et.w};
-                        cg_fix<COUNT>(b, cl, a.table, d2, r, hist);
-                        cg_combine<RGB>(r, e, acc, rk);
-                    } else {
-                        const float4 et = et_g[node];
-                        const float e[4] = {et.x, et.y, et.z, et.w};
-                        band_rd_accumulate<false, COUNT, KLDS, RGB>(b, d2, e, 1.f, acc, hist, rk);
-                    }
+        // The node test as wave-uniform lane masks (scalar logic on the ballots of the compares): which
+        // lanes visit the node, which pass the reach test, which accept it as a cluster, which open it.
+        // A mask that is a bool set in the arms of a branch comes back from the compiler as a select
+        // and a compare per use.
+        const uint64_t m_act = __builtin_amdgcn_ballot_w64(node >= resume);
+        if (COUNT && __builtin_amdgcn_inverse_ballot_w64(m_act)) ++k_nodes;
+        // distance from p to the node box per axis (0 inside the slab)
+        const float bx = fmaxf(fmaxf(h.bminx - px, px - h.bmaxx), 0.f);
+        const float by = fmaxf(fmaxf(h.bminy - py, py - h.bmaxy), 0.f);
+        const float bz = fmaxf(fmaxf(h.bminz - pz, pz - h.bmaxz), 0.f);
+        // exact-zero pruning with a 1e-4 margin (prune_f), so the test may round freely
+        const float box2 = __builtin_fmaf(bz, bz, __builtin_fmaf(by, by, bx * bx));
+        const uint64_t m_near =
+            (h.flags & NODE_BLACK) ? 0 : m_act & __builtin_amdgcn_ballot_w64(!(box2 >= box_lim));
+        if (COUNT && __builtin_amdgcn_inverse_ballot_w64(m_act)) {
+            if (h.flags & NODE_BLACK)
+                ++hist[17];
+            else if (box2 >= box_lim)
+                ++hist[16];
+        }
+        uint64_t m_open = 0;
+        if (m_near != 0) {
+            const float dx = px - h.px, dy = py - h.py, dz = pz - h.pz;
+            const float d2 = dx * dx + dy * dy + dz * dz;
+            // nodeBound.Inside(p) <=> every per-axis distance is 0 (the subtractions' signs are exact)
+            const uint64_t m_out = __builtin_amdgcn_ballot_w64(fmaxf(fmaxf(bx, by), bz) != 0.f);
+            if (COUNT && node > 0 && __builtin_amdgcn_inverse_ballot_w64(m_near & ~m_out)) ++hist[18];
+            const uint64_t m_acc = m_near & m_out & dw_below(h.sum_area, d2, a.max_error, m_lo, m_hi, m_near);
+            m_open = m_near & ~m_acc;
+            if (__builtin_amdgcn_inverse_ballot_w64(m_acc)) {
+                if (CG) {
+                    CgRec r = cg_fetch<COUNT>(b, cl, a.table, d2, hist);
+                    // Et's scalar load issued behind the record's table loads: issued before them,
+                    // the wait for the LDS step's reads (lgkmcnt) would wait for it too
+                    int nd = node;
+                    asm volatile("" : "+s"(nd)::"memory");
+                    const float4 et = et_g[nd];
+                    const float e[4] = {et.x, et.y, et.z, et.w};
+                    cg_fix<COUNT>(b, cl, a.table, d2, r, hist);
+                    cg_combine<RGB>(r, e, acc, rk);
                 } else {
-                    open = true;
+                    const float4 et = et_g[node];
+                    const float e[4] = {et.x, et.y, et.z, et.w};
+                    band_rd_accumulate<false, COUNT, KLDS, RGB>(b, d2, e, 1.f, acc, hist, rk);
                 }
             }
         }
-        const bool any_open = __builtin_amdgcn_ballot_w64(open) != 0;
+        const bool open = __builtin_amdgcn_inverse_ballot_w64(m_open);
+        const bool any_open = m_open != 0;
+        // lanes done with the subtree: pruned, accepted, or (a leaf) served below
+        const uint64_t m_closed = h.leaf_first >= 0 ? m_act : m_act & ~m_open;
+        if (__builtin_amdgcn_inverse_ballot_w64(m_closed)) resume = skip;
         if (h.leaf_first >= 0) {
             if (any_open) {
                 // the leaf's non-black points only (DeviceOctree::upload puts them first, h.pad)
                 f2v lacc[2] = {f2v{0.f, 0.f}, f2v{0.f, 0.f}};
                 const int live = (int)(h.pad & 0xffffu);
                 if (COUNT) w_pts += live;
+                if (COUNT && open) {
+                    hist[14] += KLDS > 0 && (h.pad >> 16) < lds_code && live > 1;
+                    hist[15] += live & 1;
+                }
                 int i0 = 0;
                 if (!COUNT && KLDS > 0 && (h.pad >> 16) < lds_code) {
                     for (; i0 + 1 < live; i0 += 2) {
@@ -793,7 +819,6 @@ __device__ __forceinline__ void mo_band_traverse(const BandTree &a, int grp, flo
                 acc[0] += lacc[0];
                 acc[1] += lacc[1];
             }
-            if (open) resume = skip;
             node = skip;
         } else if (any_open) {
             node = node + 1;

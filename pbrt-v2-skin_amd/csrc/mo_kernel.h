@@ -53,12 +53,13 @@ struct GatherOpts {
 // counters (nullable, q*4 int32): per query {reference-traversal nodes entered, points evaluated,
 // pruned-kernel nodes entered, points evaluated}. The packet kernel reports only
 // the last two (the first two are 0); mode 1 follows the reference summation order.
+// counts (mode 0 only, nullable): the instrumented pass's statistics, kStatStride * kGroups, added to.
 // mode: 0 spectrally sharded (default; needs `layout` for p.groups), 1 exact reference order, 2 packet.
 // work: kGroups ints of device scratch for mode 0 (the persistent grid's chunk counters); perm:
 // >= nq rounded up to 1024 ints of device scratch for mode 0 (the sorted query permutation).
 void launch_mo_gather(const DeviceOctree &t, const BandLayout *layout, const DeviceProfile &p, float max_error, int nq,
                       const float *queries, float *out, int out_stride, int32_t *counters, int *work, int *perm,
-                      int mode, const GatherOpts &opts, hipStream_t stream);
+                      int mode, const GatherOpts &opts, hipStream_t stream, unsigned long long *counts = nullptr);
 
 // launch_mo_gather's mode 1 (mo_exact.hip) and mode 2 (mo_packet.hip), behind its argument checks
 void launch_mo_exact(const DeviceOctree &t, const DeviceProfile &p, float max_error, int nq, const float *queries,
@@ -85,8 +86,11 @@ void launch_mo_rgb(const DeviceOctree &t, const float *table3, const float *rcp3
 // lookups inside the profile (lane x band), 5..7 those at entries < 4096, 8192, 16384; common grid
 // only: 8 lane-records read from the group rows (two 16-byte loads each), 9 from the LDS near field,
 // 10 from the bands' own tables (four 8-byte loads); 11..16 the L2 footprint of the row and own-table
-// fetches (mo_band.h kHist 7..12: distinct 32-B sectors, 128-B lines, wave fetches).
-constexpr int kStatStride = 4 + 13;
+// fetches (mo_band.h kHist 7..12: distinct 32-B sectors, 128-B lines, wave fetches); 17 lane-records of
+// flagged row cells; 18 lane-opens of leaves that qualify for the LDS-only pair loop, 19 of leaves with an
+// odd live count; 20 lane-visits pruned by the reach test, 21 of black nodes, 22 inside the box of a
+// node other than the root (mo_band.h kHist 13..18).
+constexpr int kStatStride = 4 + 19;
 
 // Spectrally sharded gather for the render path: queries4[i] = {p, *}, i < *count_dev (<= nq_max);
 // out4[i * 8 + g] = the 4 bands of group g (BandGroups::pos gives a band's float offset).

@@ -181,15 +181,16 @@ void launch_mo_band(const DeviceOctree &t, const BandLayout &layout, const Devic
 
 void launch_mo_gather(const DeviceOctree &t, const BandLayout *layout, const DeviceProfile &p, float max_error, int nq,
                       const float *queries, float *out, int out_stride, int32_t *counters, int *work, int *perm,
-                      int mode, const GatherOpts &opts, hipStream_t stream) {
+                      int mode, const GatherOpts &opts, hipStream_t stream, unsigned long long *counts) {
     if (nq <= 0) return;
+    if (counts && mode != 0) throw Error(-1, "launch_mo_gather: path statistics come from the sharded gather only");
     if (t.n_nodes <= 0) throw Error(-1, "launch_mo_gather: octree is empty");
     if (p.L < 2) throw Error(-1, "launch_mo_gather: profile table has fewer than 2 entries");
     if (mode == 1) return launch_mo_exact(t, p, max_error, nq, queries, out, out_stride, counters, stream);
     if (mode != 0) return launch_mo_packet(t, p, max_error, nq, queries, out, out_stride, counters, stream);
-    const bool count = counters != nullptr;
+    const bool count = counters != nullptr || counts != nullptr;
     if (!layout || !work) throw Error(-2, "launch_mo_gather: the sharded gather needs a band layout and work counters");
-    if (count) MPSS_HIP(hipMemsetAsync(counters, 0, sizeof(int32_t) * 4 * (size_t)nq, stream));
+    if (counters) MPSS_HIP(hipMemsetAsync(counters, 0, sizeof(int32_t) * 4 * (size_t)nq, stream));
     BandArgs b{};
     b.t = band_tree(t, *layout, p, max_error);
     b.queries3 = queries;
@@ -197,6 +198,7 @@ void launch_mo_gather(const DeviceOctree &t, const BandLayout *layout, const Dev
     b.out = out;
     b.out_stride = out_stride;
     b.counters = counters;
+    b.counts = counts;
     b.work = work;
     b.perm = perm;
     launch_band(b, nq, t, count, opts, stream);

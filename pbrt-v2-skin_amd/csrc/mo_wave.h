@@ -8,6 +8,8 @@
 
 namespace mpss {
 
+static_assert(kStatStride == 4 + kHist, "the statistics hold the walk's four counts and every kHist slot");
+
 // ---------------------------------------------------------------------------------------
 // Spectrally sharded gather (mo_band.h), in two launches: mo_sort_kernel sorts each 1024-query
 // chunk by a Morton key of its query positions into a permutation, then the persistent

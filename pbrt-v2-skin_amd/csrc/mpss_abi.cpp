@@ -332,6 +332,14 @@ int mpss_mo_batch(mpss_ctx *c, uint32_t id, uint32_t q, const float *p_dev, floa
     });
 }
 
+int mpss_mo_batch_paths(mpss_ctx *c, uint32_t id, uint32_t q, const float *p_dev, float *mo_dev, uint64_t *stats) {
+    return guarded([&] {
+        require(c && p_dev && mo_dev && stats && q > 0, "mpss_mo_batch_paths: null argument");
+        require(q <= (1u << 30), "mpss_mo_batch_paths: at most 2^30 queries per call");
+        reinterpret_cast<Context *>(c)->mo_batch_paths(id, (int)q, p_dev, mo_dev, stats);
+    });
+}
+
 int mpss_add_mesh(mpss_ctx *c, uint32_t nv, const float *P, const float *N, const float *S, const float *uv,
                   uint32_t nt, const int32_t *idx, const float *o2w, const float *w2o, int rev, uint32_t mat) {
     return guarded([&] {

@@ -121,6 +121,7 @@ _sig("mpss_set_irradiance_points", C.c_int, [vp, u32, f32p, f32p, f32p, f32p])
 _sig("mpss_octree_info", C.c_int, [vp, u32p, u32p, u32p])
 _sig("mpss_octree_export", C.c_int, [vp, vp, vp, vp, vp, vp])
 _sig("mpss_mo_batch", C.c_int, [vp, u32, u32, vp, vp, vp, vp])
+_sig("mpss_mo_batch_paths", C.c_int, [vp, u32, u32, vp, vp, vp])
 _sig("mpss_add_mesh", C.c_int, [vp, u32, f32p, vp, vp, vp, u32, C.POINTER(C.c_int32), f32p, f32p, C.c_int, u32])
 _sig("mpss_add_sphere_light", C.c_int, [vp, f32p, C.c_float, f32p, C.c_int])
 _sig("mpss_add_infinite_light", C.c_int, [vp, f32p, C.c_int, f32p, f32p])
@@ -672,6 +673,13 @@ class Context:
         check(_lib.mpss_octree_export(self.h, *[d[k].ctypes.data_as(vp) for k in
                                                 ("nodes", "node_et", "pt_hdr", "pt_e", "pt_index")]))
         return d
+
+    def mo_batch_paths(self, mid, q, p_dev, mo_dev):
+        """mpss_mo_batch_paths: the sharded gather's instrumented pass, its statistics as an (8, 23) uint64
+        array (per band group; the slots are listed in include/mpss.h)."""
+        stats = np.zeros((8, 23), np.uint64)
+        check(_lib.mpss_mo_batch_paths(self.h, mid, q, p_dev, mo_dev, stats.ctypes.data))
+        return stats
 
     def mo_batch(self, mid, q, p_dev, mo_dev, counters_dev=None, stream=None):
         check(_lib.mpss_mo_batch(self.h, mid, q, p_dev, mo_dev, counters_dev, stream))
