@@ -248,6 +248,14 @@ int mpss_add_imagemap(mpss_ctx *ctx, const mpss_imagemap *t, uint32_t *texture_i
  * (a float imagemap, Material::Bump on the shading geometry; -1: none). The albedo texture is
  * evaluated per irradiance point (no differentials) and per camera hit (ray differentials). */
 int mpss_set_material_textures(mpss_ctx *ctx, uint32_t material_id, int32_t albedo_texture, int32_t bump_texture);
+/* LayeredSkin's "texture Kr" / "texture Kt" (layeredskin.cpp:139-167): spectrum imagemaps evaluated at
+ * every camera hit's shading geometry (after Bump) with the ray differentials; the hit's Microfacet /
+ * MicrofacetTransmission lobe exists only where the lookup's spectrum is not black. -1: the constant
+ * Kr[] / Kt[] of mpss_layeredskin; any negative id is taken as -1, as mpss_set_material_textures takes
+ * it. MPSS_ERR_INVALID for an unknown material or texture id, a float texture, or a dipole material. Independent of mpss_set_material_textures (neither resets the other's
+ * bindings); kept by mpss_update_layeredskin; no new Preprocess is needed. Added within ABI version 13:
+ * detect it by symbol. */
+int mpss_set_material_spec_textures(mpss_ctx *ctx, uint32_t material_id, int32_t kr_texture, int32_t kt_texture);
 
 /* Irradiance points (IrradiancePoint p, n, E, area; irradiancepoint.h:36-45) -> device octree. */
 int mpss_set_irradiance_points(mpss_ctx *ctx, uint32_t n, const float *p, const float *nrm, const float *E,

@@ -361,6 +361,8 @@ void Context::update_layeredskin(uint32_t id, const mpss_layeredskin &m) {
     const Material &old = *materials_[id];
     mat->albedo_tex = old.albedo_tex;
     mat->bump_tex = old.bump_tex;
+    mat->kr_tex = old.kr_tex;
+    mat->kt_tex = old.kt_tex;
     // (neither point finder reads a material's BSSRDF state today; dropped all the same when it flips)
     if (mat->no_bssrdf != old.no_bssrdf) invalidate_points_locked();
     materials_[id] = std::move(mat);
@@ -498,6 +500,28 @@ void Context::set_material_textures(uint32_t material, int albedo, int bump) {
     materials_[material]->albedo_tex = albedo;
     materials_[material]->bump_tex = bump;
     mark_scene_dirty_locked();  // (tessellation displaces the points along the bump map)
+}
+
+// "texture Kr" / "texture Kt" of LayeredSkin: only the per-hit BSDF reads them (GetBSDF), so the points and
+// their irradiance stay; the RenderMaterial records are rebuilt before the next render.
+void Context::set_material_spec_textures(uint32_t material, int kr, int kt) {
+    std::lock_guard<std::mutex> g(mu_);
+    if (material >= materials_.size())
+        throw Error(MPSS_ERR_INVALID, "set_material_spec_textures: unknown material id");
+    if (materials_[material]->dipole)
+        throw Error(MPSS_ERR_INVALID, "set_material_spec_textures: a dipole material is an Rd functor, not a surface");
+    auto check = [&](int id, const char *what) {
+        if (id < 0) return;
+        if (id >= (int)textures_.size())
+            throw Error(MPSS_ERR_INVALID, std::string("set_material_spec_textures: unknown texture id for ") + what);
+        if (textures_[id]->py.nch == 1)
+            throw Error(MPSS_ERR_INVALID, std::string("set_material_spec_textures: ") + what + " needs a spectrum texture");
+    };
+    check(kr, "Kr");
+    check(kt, "Kt");
+    materials_[material]->kr_tex = kr < 0 ? -1 : kr;
+    materials_[material]->kt_tex = kt < 0 ? -1 : kt;
+    materials_dirty_ = true;
 }
 
 std::vector<const TexView *> Context::host_bump_views() const {

@@ -37,6 +37,7 @@ struct Material {
     DeviceProfile dev_profile;
     DevBuf<float> dev_rho;  // [n_rho]
     int albedo_tex = -1, bump_tex = -1;  // ImageTexture ids ("texture albedo" / "texture bumpmap")
+    int kr_tex = -1, kt_tex = -1;        // ... ("texture Kr" / "texture Kt"): evaluated per camera hit
     // rgbprofile (ComputeRGBMultipoleProfile): Rd = FromRGB of three tables, Mo() in the
     // reference-order gather; dev_rgb [3][L] (rows 0..2 of profile.table), rgb_rcp their rcp
     bool rgb = false;
@@ -79,7 +80,7 @@ struct RenderWorkspace {
     DevBuf<uint32_t> flags, hs, spill;
     DevBuf<int32_t> slot;
     DevBuf<int> count, work, perm;  // perm: the sharded gather's sorted query ids
-    DevBuf<float4> q, mo, ha, hb, xyz, alb, frame, st;
+    DevBuf<float4> q, mo, ha, hb, xyz, alb, frame, st, kr, kt;
     DevBuf<unsigned char> terms;
     DevBuf<float> ld;
     // reference-sampler replay: the batch's window table and the render tasks' stream cursors
@@ -131,6 +132,7 @@ public:
     void export_octree(void *nodes, float *node_et, float *pt_hdr, float *pt_e, int32_t *pt_index);
     uint32_t add_imagemap(const mpss_imagemap &m);
     void set_material_textures(uint32_t material, int albedo, int bump);
+    void set_material_spec_textures(uint32_t material, int kr, int kt);
     std::vector<const TexView *> host_bump_views() const;
     float max_error() const { return max_error_; }
     GatherOpts gather_opts() const {

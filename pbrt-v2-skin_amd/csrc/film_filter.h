@@ -22,6 +22,8 @@ __device__ __forceinline__ void image_sample_keyed(uint32_t seed, uint32_t key, 
 __global__ void primary_filter_kernel(RenderScene sc, PieceList pl, SampleRecs rec0, FilterGeom fg);
 __global__ void shade_tex_filter_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed, int max_hits,
                                         FilterGeom fg);
+__global__ void shade_tex_filter_spec_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed, int max_hits,
+                                        FilterGeom fg);
 __global__ void film_filter_kernel(RenderScene sc, PieceList pl, SampleRecs rec0, FilmFilter f);
 
 }  // namespace mpss

@@ -1,7 +1,8 @@
 // filter_pass.hip -- the camera pass and the texture lookups of a render batch under a non-default pixel
 // filter (pixel_filter.h, DESIGN.md "Pixel filters"):
 //   primary_filter_kernel    primary_kernel (primary.hip) over pieces of the film's sample extent
-//   shade_tex_filter_kernel  shade_tex_kernel (shade.hip) for hits of such pieces
+//   shade_tex_filter_kernel  shade_tex_kernel (shade.hip) for hits of such pieces, and its instance
+//                            shade_tex_filter_spec_kernel (shade_tex_spec_kernel) for Kr / Kt textures
 // Each follows its model line for line except where the filter shows, marked "filter:" below. They are
 // kernels of their own, in a unit of their own, so that the default filter's kernels keep their code
 // objects to the instruction (as instances of one template the default kernels came out reordered).
@@ -10,6 +11,7 @@
 #include "bvh_trace.h"
 #include "film_filter.h"
 #include "geom.h"
+#include "spectrum_tables.h"
 #include "texture.h"
 
 namespace mpss {
@@ -87,8 +89,9 @@ __global__ __launch_bounds__(256) void primary_filter_kernel(RenderScene sc, Pie
     }
 }
 
-__global__ __launch_bounds__(256) void shade_tex_filter_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
-                                                               int max_hits, FilterGeom fg) {
+template <bool kSpec>
+__device__ __forceinline__ void shade_tex_filter(const RenderScene &sc, const SampleRecs &rec, int spp, uint32_t seed,
+                                                 int max_hits, const FilterGeom &fg) {
     const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int nhits = *rec.hit_count;
     if (slot >= nhits || slot >= max_hits) return;
@@ -96,7 +99,7 @@ __global__ __launch_bounds__(256) void shade_tex_filter_kernel(RenderScene sc, S
     if (hs & HS_LIGHT) return;
     const RenderMaterial &mat = sc.materials[(hs >> REC_MAT_SHIFT) & 0xffu];
     const bool want_alb = (hs >> 31) && mat.has_alb_tex;
-    if (!want_alb && !mat.has_bump) return;
+    if (!want_alb && !mat.has_bump && !(kSpec && (mat.has_kr_tex || mat.has_kt_tex))) return;
     const float4 ha = rec.hit_a[slot], hb = rec.hit_b[slot];
     const int s = (int)(hs & 0xffffu), tri = __float_as_int(ha.w);
     const uint32_t pix = __float_as_uint(hb.w);
@@ -133,6 +136,18 @@ __global__ __launch_bounds__(256) void shade_tex_filter_kernel(RenderScene sc, S
         rec.hit_frame[2 * (size_t)slot] = make_float4(nn_b.x, nn_b.y, nn_b.z, 0.f);
         rec.hit_frame[2 * (size_t)slot + 1] = make_float4(sn.x, sn.y, sn.z, 0.f);
     }
+    if (kSpec) {
+        if (mat.has_kr_tex) rec.hit_kr[slot] = spec_lookup(mat.kr_tex, g);
+        if (mat.has_kt_tex) rec.hit_kt[slot] = spec_lookup(mat.kt_tex, g);
+    }
+}
+__global__ __launch_bounds__(256) void shade_tex_filter_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
+                                                               int max_hits, FilterGeom fg) {
+    shade_tex_filter<false>(sc, rec, spp, seed, max_hits, fg);
+}
+__global__ __launch_bounds__(256) void shade_tex_filter_spec_kernel(RenderScene sc, SampleRecs rec, int spp,
+                                                                    uint32_t seed, int max_hits, FilterGeom fg) {
+    shade_tex_filter<true>(sc, rec, spp, seed, max_hits, fg);
 }
 
 }  // namespace mpss

@@ -212,6 +212,13 @@ int mpss_set_material_textures(mpss_ctx *c, uint32_t mid, int32_t albedo, int32_
     });
 }
 
+int mpss_set_material_spec_textures(mpss_ctx *c, uint32_t mid, int32_t kr, int32_t kt) {
+    return guarded([&] {
+        require(c != nullptr, "mpss_set_material_spec_textures: null context");
+        reinterpret_cast<Context *>(c)->set_material_spec_textures(mid, kr, kt);
+    });
+}
+
 int mpss_set_material_tables(mpss_ctx *c, const float *rd, uint32_t len, const float *rcp, const float *rho,
                              uint32_t n_rho, const float *albedo, int is_mc, uint32_t *id) {
     return guarded([&] {

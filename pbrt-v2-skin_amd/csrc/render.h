@@ -54,6 +54,10 @@ struct RenderMaterial {
     // nonzero R[c] and the largest (0, 0 when R is black)
     float r_lo, r_hi;
     int r_nonneg;
+    // ImageTexture "Kr" / "Kt" (layeredskin.cpp:154-155): the hit's R / T is FromRGB of the lookup at its
+    // shading geometry, and its lobe set follows that spectrum's blackness (the *_spec_kernel instances)
+    int has_kr_tex, has_kt_tex;
+    TexView kr_tex, kt_tex;
 };
 
 struct RenderScene {
@@ -81,6 +85,7 @@ struct RenderScene {
     int replay_k, replay_spp, replay_x0, replay_y0, replay_w;
     int64_t replay_npix;
     const uint32_t *irr_scr;  // [point][light][2] IrradianceTask Sample02 scrambles
+    int any_spec_tex;  // some material has a Kr or Kt texture: the *_spec_kernel instances run
 };
 
 // The GPU replay of the reference's render-task streams for one window of the sample extent
@@ -179,6 +184,9 @@ struct SampleRecs {
     float4 *xyz;     // [hits] the sample's filtered XYZ (assemble_kernel)
     float4 *hit_alb; // [hits] albedo texture lookup (RGB) of a textured BSSRDF hit (shade_tex_kernel)
     float4 *hit_frame; // [hits][2] bump-mapped shading normal nn and dpdu direction sn (shade_tex_kernel)
+    // [hits] Kr / Kt texture lookups (RGB) of a mesh hit whose material has them; w: 1 when FromRGB of the
+    // lookup is not black, else 0 (shade_tex_spec_kernel; allocated when RenderScene::any_spec_tex)
+    float4 *hit_kr, *hit_kt;
 };
 
 // SurfacePointTask's random-walk paths (usepoissonpointfinder): one lane per path, candidates of
@@ -208,6 +216,15 @@ __global__ void shade_direct_kernel(RenderScene sc, SampleRecs rec, int spp, uin
 // 1/sqrt(spp)), ComputeDifferentials, the albedo lookup (-> hit_alb) and the bumped shading frame
 // (-> hit_frame), before shade_direct_kernel reads them.
 __global__ void shade_tex_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed, int max_hits);
+// The instances of a scene with Kr / Kt textures (RenderScene::any_spec_tex): shade_tex_spec_kernel also
+// looks those up for every mesh hit (-> hit_kr, hit_kt); shade_direct_spec_kernel and
+// direct_combine_spec_kernel take a hit's R, T and lobe set from them.
+__global__ void shade_tex_spec_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed, int max_hits);
+__global__ void shade_direct_spec_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed, int max_hits,
+                                         int ns_max, DirectTerms *terms, float4 *inf_st);
+template <bool kInf>
+__global__ void direct_combine_spec_kernel(RenderScene sc, SampleRecs rec, int max_hits, int ns_max,
+                                           const DirectTerms *terms, const float4 *inf_st);
 __global__ void shade_nolight_kernel(RenderScene sc, SampleRecs rec, int max_hits);
 template <bool kInf>
 __global__ void direct_combine_kernel(RenderScene sc, SampleRecs rec, int max_hits, int ns_max,

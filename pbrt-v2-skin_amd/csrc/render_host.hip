@@ -119,7 +119,8 @@ struct Context::TileCall {
     // (the per-hit pointers are valid after batch_reserve_hits)
     SampleRecs recs() const {
         return SampleRecs{ws->flags.ptr, ws->spill.ptr, ws->slot.ptr, ws->ld.ptr, ws->ha.ptr, ws->hb.ptr, ws->hs.ptr,
-                          ws->q.ptr,     ws->count.ptr, ws->mo.ptr,   ws->xyz.ptr, ws->alb.ptr, ws->frame.ptr};
+                          ws->q.ptr,     ws->count.ptr, ws->mo.ptr,   ws->xyz.ptr, ws->alb.ptr, ws->frame.ptr,
+                          ws->kr.ptr,    ws->kt.ptr};
     }
 };
 
@@ -204,6 +205,10 @@ void Context::batch_reserve_hits(const TileCall &c, const RenderScene &sc, int64
         ws->reserve(ws->alb, (size_t)nh);
         ws->reserve(ws->frame, (size_t)nh * 2);
     }
+    if (sc.any_spec_tex) {
+        ws->reserve(ws->kr, (size_t)nh);
+        ws->reserve(ws->kt, (size_t)nh);
+    }
 }
 
 // texture lookups, then UniformSampleAllLights: a lane per (hit, light, light sample), combined per hit
@@ -224,7 +229,17 @@ void Context::batch_direct(TileCall &c, const RenderScene &sc, int64_t nh) {
     const SampleRecs rec = c.recs();
     const dim3 per_hit((unsigned)((nh + 255) / 256));
     hipEvent_t ev{};
-    if (sc.any_tex) {
+    // a scene with Kr / Kt textures (any_spec_tex) runs the *_spec_kernel instances, every other scene the
+    // kernels it always ran
+    if (sc.any_spec_tex) {
+        time_begin(c.timing, stream, ev);
+        if (c.filtered)
+            hipLaunchKernelGGL(shade_tex_filter_spec_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed,
+                               (int)nh, c.ff.g);
+        else
+            hipLaunchKernelGGL(shade_tex_spec_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh);
+        time_end(c.timing, stream, ev, 5, c.timed);
+    } else if (sc.any_tex) {
         time_begin(c.timing, stream, ev);
         if (c.filtered)
             hipLaunchKernelGGL(shade_tex_filter_kernel, per_hit, dim3(256), 0, stream, sc, rec, c.spp, c.seed, (int)nh,
@@ -234,7 +249,16 @@ void Context::batch_direct(TileCall &c, const RenderScene &sc, int64_t nh) {
         time_end(c.timing, stream, ev, 5, c.timed);
     }
     time_begin(c.timing, stream, ev);
-    if (c.nlights > 0) {
+    if (c.nlights > 0 && sc.any_spec_tex) {
+        hipLaunchKernelGGL(shade_direct_spec_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, sc,
+                           rec, c.spp, c.seed, (int)nh, c.ns_max, terms, inf_st);
+        if (sc.n_infinite > 0)
+            hipLaunchKernelGGL(direct_combine_spec_kernel<true>, per_hit, dim3(256), 0, stream, sc, rec, (int)nh,
+                               c.ns_max, (const DirectTerms *)terms, (const float4 *)inf_st);
+        else
+            hipLaunchKernelGGL(direct_combine_spec_kernel<false>, per_hit, dim3(256), 0, stream, sc, rec, (int)nh,
+                               c.ns_max, (const DirectTerms *)terms, (const float4 *)nullptr);
+    } else if (c.nlights > 0) {
         hipLaunchKernelGGL(shade_direct_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, sc, rec,
                            c.spp, c.seed, (int)nh, c.ns_max, terms, inf_st);
         if (sc.n_infinite > 0)

@@ -304,6 +304,14 @@ void Context::upload_materials() {
             r.has_bump = 1;
             r.bump_tex = textures_[m.bump_tex]->device_view(d_lut_.ptr);
         }
+        if (m.kr_tex >= 0) {
+            r.has_kr_tex = 1;
+            r.kr_tex = textures_[m.kr_tex]->device_view(d_lut_.ptr);
+        }
+        if (m.kt_tex >= 0) {
+            r.has_kt_tex = 1;
+            r.kt_tex = textures_[m.kt_tex]->device_view(d_lut_.ptr);
+        }
         rmat.push_back(r);
     }
     d_materials_.upload(rmat.data(), rmat.size());
@@ -339,6 +347,7 @@ RenderScene Context::render_scene() const {
     sc.dy_camera[1] = dy.y;
     sc.dy_camera[2] = dy.z;
     for (const auto &m : materials_) sc.any_tex |= (m->albedo_tex >= 0 || m->bump_tex >= 0);
+    for (const auto &m : materials_) sc.any_spec_tex |= (m->kr_tex >= 0 || m->kt_tex >= 0);
     return sc;
 }
 

@@ -4,9 +4,12 @@
 //   shade_direct_kernel    one EstimateDirect per lane (core/integrator.cpp:117-174)
 //   shade_nolight_kernel   a scene without lights
 //   direct_combine_kernel  UniformSampleAllLights' per-band sums (integrator.cpp:47-77)
+// and their *_spec_kernel instances for a scene with Kr / Kt textures (RenderScene::any_spec_tex), where a
+// hit's R, T and lobe set come from its own lookups (HitSpec); every other scene runs the kernels above.
 #include "render.h"
 
 #include <climits>
+#include <type_traits>
 
 #include "bvh_trace.h"
 #include "geom.h"
@@ -31,27 +34,74 @@ struct Lobe {
     float a, b, c, d;
 };
 
-// The shading point's BSDF is a mesh material's (mat), or -- mat == nullptr -- the default matte of a
-// light sphere seen directly (geom.h kMatteF): kind 3, f = 0 + R * INV_PI on the reflection side.
-__device__ __forceinline__ Lobe bsdf_lobe(const RenderMaterial *mat, bool refl, V3 wo_l, V3 wi_l) {
+// What GetBSDF makes of Kr and Kt at a mesh hit (layeredskin.cpp:154-161): R, T, and which of the two
+// lobes exist (!R.IsBlack(), !T.IsBlack()). MatSpec: constant Kr / Kt, the material's record. HitSpec: a
+// scene with Kr / Kt textures -- a textured side is FromRGB of the hit's lookup (ImageTexture's
+// convertOut; hit_kr / hit_kt, whose w is that spectrum's blackness test), the other side the material's.
+struct MatSpec {
+    const RenderMaterial *mat;
+    __device__ __forceinline__ int has_refl() const { return mat->has_refl; }
+    __device__ __forceinline__ int has_trans() const { return mat->has_trans; }
+    __device__ __forceinline__ float R(int c) const { return mat->R[c]; }
+    __device__ __forceinline__ float T(int c) const { return mat->T[c]; }
+};
+struct HitSpec {
+    const RenderMaterial *mat;
+    int refl, trans;
+    bool r_tex, t_tex;
+    ReflSplit r, t;
+    __device__ __forceinline__ int has_refl() const { return refl; }
+    __device__ __forceinline__ int has_trans() const { return trans; }
+    __device__ __forceinline__ float R(int c) const { return r_tex ? refl_split_band(r, c) : mat->R[c]; }
+    __device__ __forceinline__ float T(int c) const { return t_tex ? refl_split_band(t, c) : mat->T[c]; }
+};
+template <bool kSpec>
+using SpecOf = std::conditional_t<kSpec, HitSpec, MatSpec>;
+__device__ __forceinline__ void load_spec(MatSpec &b, const RenderMaterial *mat, const SampleRecs &, int) { b.mat = mat; }
+__device__ __forceinline__ void load_spec(HitSpec &b, const RenderMaterial *mat, const SampleRecs &rec, int slot) {
+    b = HitSpec{};
+    b.mat = mat;
+    if (!mat) return;  // a light sphere's surface
+    b.refl = mat->has_refl;
+    b.trans = mat->has_trans;
+    if (mat->has_kr_tex) {
+        const float4 k = rec.hit_kr[slot];
+        b.r_tex = true;
+        b.r = refl_split(k.x, k.y, k.z);
+        b.refl = k.w != 0.f;
+    }
+    if (mat->has_kt_tex) {
+        const float4 k = rec.hit_kt[slot];
+        b.t_tex = true;
+        b.t = refl_split(k.x, k.y, k.z);
+        b.trans = k.w != 0.f;
+    }
+}
+
+// The shading point's BSDF is a mesh material's (b.mat, with the hit's R / T / lobe set b), or -- b.mat ==
+// nullptr -- the default matte of a light sphere seen directly (geom.h kMatteF): kind 3, f = 0 + R * INV_PI
+// on the reflection side.
+template <class B>
+__device__ __forceinline__ Lobe bsdf_lobe(const B &b, bool refl, V3 wo_l, V3 wi_l) {
     Lobe L{0u, 0.f, 0.f, 0.f, 1.f};
-    if (!mat) {
+    if (!b.mat) {
         if (refl) L = Lobe{3u, 0.f + kMatteF, 0.f, 0.f, 1.f};
     } else if (refl) {  // the ng test keeps BRDFs only
-        if (mat->has_refl) {
-            const MfTerms t = microfacet_terms(mat->mf, wo_l, wi_l);
+        if (b.has_refl()) {
+            const MfTerms t = microfacet_terms(b.mat->mf, wo_l, wi_l);
             if (!t.zero) L = Lobe{1u, t.D, t.G, t.F, t.den};
         }
-    } else if (mat->has_trans) {  // ... or BTDFs only
-        const MtTerms t = mt_terms_ool(mat->mf, wo_l, wi_l);
+    } else if (b.has_trans()) {  // ... or BTDFs only
+        const MtTerms t = mt_terms_ool(b.mat->mf, wo_l, wi_l);
         if (!t.zero) L = Lobe{2u, t.s, t.F, 0.f, 1.f};
     }
     return L;
 }
 
-__device__ __forceinline__ float lobe_value(const RenderMaterial *mat, const Lobe &L, int c) {
+template <class B>
+__device__ __forceinline__ float lobe_value(const B &b, const Lobe &L, int c) {
     if (L.kind == 3u) return L.a;
-    return L.kind == 1u ? mat->R[c] * L.a * L.b * L.c / L.d : (mat->T[c] * L.a) * (1.f - L.b);
+    return L.kind == 1u ? b.R(c) * L.a * L.b * L.c / L.d : (b.T(c) * L.a) * (1.f - L.b);
 }
 
 // x / d (IEEE, correctly rounded) for many x over one d, from inv = x-independent RN(1 / d): with
@@ -76,28 +126,30 @@ __device__ __forceinline__ Den make_den(float d) {
     return Den{d, 1.f / d, ad >= 0x1p-60f && ad <= 0x1p60f};
 }
 // lobe_value with the reflection lobe's division by L.d done through den = make_den(L.d)
-__device__ __forceinline__ float lobe_value_den(const RenderMaterial *mat, const Lobe &L, int c, const Den &den) {
+template <class B>
+__device__ __forceinline__ float lobe_value_den(const B &b, const Lobe &L, int c, const Den &den) {
     if (L.kind == 3u) return L.a;
-    return L.kind == 1u ? div_by(mat->R[c] * L.a * L.b * L.c, den.d, den.inv, den.ok)
-                        : (mat->T[c] * L.a) * (1.f - L.b);
+    return L.kind == 1u ? div_by(b.R(c) * L.a * L.b * L.c, den.d, den.inv, den.ok) : (b.T(c) * L.a) * (1.f - L.b);
 }
 
-__device__ __forceinline__ bool lobe_black(const RenderMaterial *mat, const Lobe &L) {
+template <class B>
+__device__ __forceinline__ bool lobe_black(const B &b, const Lobe &L) {
     if (L.kind == 0u) return true;
     if (L.kind == 3u) return false;
     for (int c = 0; c < NB; ++c)
-        if (lobe_value(mat, L, c) != 0.f) return false;
+        if (lobe_value(b, L, c) != 0.f) return false;
     return true;
 }
 
 // BSDF::Pdf (reflection.cpp:736-751): mean of the matching lobes' pdfs, R then T
-__device__ __forceinline__ float bsdf_pdf(const RenderMaterial *mat, V3 wo_l, V3 wi_l) {
-    if (!mat) return lambert_pdf(wo_l, wi_l);  // (0 + pdf) / 1
-    const int n = mat->has_refl + mat->has_trans;
+template <class B>
+__device__ __forceinline__ float bsdf_pdf(const B &b, V3 wo_l, V3 wi_l) {
+    if (!b.mat) return lambert_pdf(wo_l, wi_l);  // (0 + pdf) / 1
+    const int n = b.has_refl() + b.has_trans();
     if (n == 0) return 0.f;
     float pdf = 0.f;
-    if (mat->has_refl) pdf += microfacet_pdf(mat->mf, wo_l, wi_l);
-    if (mat->has_trans) pdf += mt_pdf_ool(mat->mf, wo_l, wi_l);
+    if (b.has_refl()) pdf += microfacet_pdf(b.mat->mf, wo_l, wi_l);
+    if (b.has_trans()) pdf += mt_pdf_ool(b.mat->mf, wo_l, wi_l);
     return pdf / (float)n;
 }
 
@@ -115,9 +167,11 @@ struct DirectTerms {       // 16 words: one EstimateDirect
 };
 static_assert(sizeof(DirectTerms) == 64, "one 64-B record per light sample");
 
-__global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
-                                                           int max_hits, int ns_max, DirectTerms *terms,
-                                                           float4 *__restrict__ inf_st) {
+// kSpec: the hit's R, T and lobe set from its Kr / Kt lookups (HitSpec) -- shade_direct_spec_kernel
+template <bool kSpec>
+__device__ __forceinline__ void shade_direct(const RenderScene &sc, const SampleRecs &rec, int spp, uint32_t seed,
+                                             int max_hits, int ns_max, DirectTerms *terms,
+                                             float4 *__restrict__ inf_st) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int per_hit = sc.nlights * ns_max;
     const int nhits = *rec.hit_count;
@@ -169,7 +223,9 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, Sampl
         rec.hit_q[slot] = make_float4(fr.p.x, fr.p.y, fr.p.z, sss ? ct : -1.f);
         if (j >= ns) return;
     }
-    const int ncomp = mat ? mat->has_refl + mat->has_trans : 1;
+    SpecOf<kSpec> bs;
+    load_spec(bs, mat, rec, slot);
+    const int ncomp = mat ? bs.has_refl() + bs.has_trans() : 1;
     const V3 wo_l = to_local(fr, wo);
     const float ng_wo = dot(wo, fr.ng);
     // LightSample(sample, offsets, j) / BSDFSample(sample, offsets, j) (light.cpp, reflection.cpp)
@@ -197,9 +253,9 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, Sampl
     float4 st = make_float4(ls.ms, ls.mt, 0.f, 0.f);
     if (lightPdf > 0.f && ls.nonblack && ncomp > 0) {
         const V3 wi_l = to_local(fr, ls.wi);
-        const Lobe f1 = bsdf_lobe(mat, dot(ls.wi, fr.ng) * ng_wo > 0.f, wo_l, wi_l);
-        if (!lobe_black(mat, f1) && !trace_any_wave(sc, ls.so, ls.sd, ls.smint, ls.smaxt, true, false, true)) {
-            const float bsdfPdf = bsdf_pdf(mat, wo_l, wi_l);
+        const Lobe f1 = bsdf_lobe(bs, dot(ls.wi, fr.ng) * ng_wo > 0.f, wo_l, wi_l);
+        if (!lobe_black(bs, f1) && !trace_any_wave(sc, ls.so, ls.sd, ls.smint, ls.smaxt, true, false, true)) {
+            const float bsdfPdf = bsdf_pdf(bs, wo_l, wi_l);
             const float w = power_heuristic(lightPdf, bsdfPdf);
             out.k1 = absdot(ls.wi, fr.nn) * w / lightPdf;
             out.l1 = f1;
@@ -209,7 +265,7 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, Sampl
     if (ncomp > 0) {
         int which = (int)floorf(ubc * (float)ncomp);
         which = which < ncomp - 1 ? which : ncomp - 1;
-        const bool pick_t = mat && (!mat->has_refl || which == 1);
+        const bool pick_t = mat && (!bs.has_refl() || which == 1);
         V3 wi_l;
         float bsdfPdf;
         if (!mat)
@@ -224,8 +280,8 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, Sampl
                 bsdfPdf += pick_t ? microfacet_pdf(mat->mf, wo_l, wi_l) : mt_pdf_ool(mat->mf, wo_l, wi_l);
                 bsdfPdf /= (float)ncomp;
             }
-            const Lobe f2 = bsdf_lobe(mat, dot(wi, fr.ng) * ng_wo > 0.f, wo_l, wi_l);
-            if (!lobe_black(mat, f2) && bsdfPdf > 0.f) {
+            const Lobe f2 = bsdf_lobe(bs, dot(wi, fr.ng) * ng_wo > 0.f, wo_l, wi_l);
+            if (!lobe_black(bs, f2) && bsdfPdf > 0.f) {
                 lightPdf = L.kind ? infinite_pdf(L, wi) : sphere_pdf(L.s, fr.p, wi);
                 if (lightPdf != 0.f) {
                     const float w = power_heuristic(bsdfPdf, lightPdf);
@@ -279,14 +335,28 @@ __global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, Sampl
     terms[gid] = out;
     if (L.kind) inf_st[gid] = st;
 }
+__global__ __launch_bounds__(256) void shade_direct_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
+                                                           int max_hits, int ns_max, DirectTerms *terms,
+                                                           float4 *__restrict__ inf_st) {
+    shade_direct<false>(sc, rec, spp, seed, max_hits, ns_max, terms, inf_st);
+}
+__global__ __launch_bounds__(256) void shade_direct_spec_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
+                                                                int max_hits, int ns_max, DirectTerms *terms,
+                                                                float4 *__restrict__ inf_st) {
+    shade_direct<true>(sc, rec, spp, seed, max_hits, ns_max, terms, inf_st);
+}
 
 // ------------------------------------------------------------------ textures
 // Li's GetBSDF / GetMultipoleBSSRDF for materials with an albedo texture or a bump map: the
 // camera RayDifferential (PerspectiveCamera::GenerateRayDifferential, perspective.cpp:81-113,
 // ScaleDifferentials(1 / sqrtf(spp)), samplerrenderer.cpp:90-91), dg.ComputeDifferentials, then
 // albedo->Evaluate(dgShading) (layeredskin.cpp:180-185) and Bump (layeredskin.cpp:143-146).
-__global__ __launch_bounds__(256) void shade_tex_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
-                                                        int max_hits) {
+// kSpec (shade_tex_spec_kernel): also Kr->Evaluate(dgs) / Kt->Evaluate(dgs) of GetBSDF (layeredskin.cpp:
+// 154-155) for every mesh hit of a material with such a texture. dgs is the bumped geometry, whose u, v and
+// differentials are dgShading's (Bump copies them, core/material.cpp:93).
+template <bool kSpec>
+__device__ __forceinline__ void shade_tex(const RenderScene &sc, const SampleRecs &rec, int spp, uint32_t seed,
+                                          int max_hits) {
     const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int nhits = *rec.hit_count;
     if (slot >= nhits || slot >= max_hits) return;
@@ -294,7 +364,7 @@ __global__ __launch_bounds__(256) void shade_tex_kernel(RenderScene sc, SampleRe
     if (hs & HS_LIGHT) return;
     const RenderMaterial &mat = sc.materials[(hs >> REC_MAT_SHIFT) & 0xffu];
     const bool want_alb = (hs >> 31) && mat.has_alb_tex;
-    if (!want_alb && !mat.has_bump) return;
+    if (!want_alb && !mat.has_bump && !(kSpec && (mat.has_kr_tex || mat.has_kt_tex))) return;
     const float4 ha = rec.hit_a[slot], hb = rec.hit_b[slot];
     const int s = (int)(hs & 0xffffu), tri = __float_as_int(ha.w);
     const uint32_t pix = __float_as_uint(hb.w);
@@ -330,6 +400,18 @@ __global__ __launch_bounds__(256) void shade_tex_kernel(RenderScene sc, SampleRe
         rec.hit_frame[2 * (size_t)slot] = make_float4(nn_b.x, nn_b.y, nn_b.z, 0.f);
         rec.hit_frame[2 * (size_t)slot + 1] = make_float4(sn.x, sn.y, sn.z, 0.f);
     }
+    if (kSpec) {
+        if (mat.has_kr_tex) rec.hit_kr[slot] = spec_lookup(mat.kr_tex, g);
+        if (mat.has_kt_tex) rec.hit_kt[slot] = spec_lookup(mat.kt_tex, g);
+    }
+}
+__global__ __launch_bounds__(256) void shade_tex_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
+                                                        int max_hits) {
+    shade_tex<false>(sc, rec, spp, seed, max_hits);
+}
+__global__ __launch_bounds__(256) void shade_tex_spec_kernel(RenderScene sc, SampleRecs rec, int spp, uint32_t seed,
+                                                             int max_hits) {
+    shade_tex<true>(sc, rec, spp, seed, max_hits);
 }
 
 // A scene without lights: no direct light and (Preprocess returned early) no octree.
@@ -347,7 +429,8 @@ __global__ __launch_bounds__(256) void shade_nolight_kernel(RenderScene sc, Samp
 // path (RN(x inv) and one Markstein correction) with no per-band range test: the same values. R, D, G, F
 // >= 0, so x >= +0. r_lo / r_hi bound R's nonzero values; the factor-2 margins absorb the roundings of
 // the bound's own products and of x's (a few ulps).
-__device__ __forceinline__ bool refl_quotients_safe(const RenderMaterial &m, const Lobe &L, const Den &den) {
+template <class M>  // M: R's range -- the material's record, or a textured hit's own (HitBands)
+__device__ __forceinline__ bool refl_quotients_safe(const M &m, const Lobe &L, const Den &den) {
     if (!den.ok || !m.r_nonneg || !(L.a >= 0.f && L.b >= 0.f && L.c >= 0.f)) return false;
     if (L.a == 0.f || L.b == 0.f || L.c == 0.f || m.r_hi == 0.f) return true;  // every x = +0: q = +-0 exactly
     const float abc = (L.a * L.b) * L.c;
@@ -355,15 +438,55 @@ __device__ __forceinline__ bool refl_quotients_safe(const RenderMaterial &m, con
     return lo >= 0x1p-99f && hi <= 0x1p99f && lo * ai >= 0x1p-99f && hi * ai <= 0x1p99f;
 }
 
+// direct_combine's view of a hit's R and T. MatBands: the material's record. HitBands (a scene with Kr / Kt
+// textures): R's 30 bands in registers, formed once per hit (every light sample multiplies them), with
+// their range for refl_quotients_safe found as upload_materials finds a material's -- a texture with a
+// negative shift or a NaN texel is no promise of R >= 0, so r_nonneg is tested band by band; T, read only
+// by the rare transmission terms, band by band from the hit's lookup.
+struct MatBands {
+    const RenderMaterial *mat;
+    __device__ __forceinline__ float R(int c) const { return mat->R[c]; }
+    __device__ __forceinline__ float T(int c) const { return mat->T[c]; }
+    __device__ __forceinline__ const RenderMaterial &range() const { return *mat; }
+};
+struct HitBands {
+    HitSpec h;
+    float Rv[NB];
+    float r_lo, r_hi;
+    int r_nonneg;
+    __device__ __forceinline__ float R(int c) const { return Rv[c]; }
+    __device__ __forceinline__ float T(int c) const { return h.T(c); }
+    __device__ __forceinline__ const HitBands &range() const { return *this; }
+};
+__device__ __forceinline__ void load_bands(MatBands &b, const RenderMaterial *mat, const SampleRecs &, int) { b.mat = mat; }
+__device__ __forceinline__ void load_bands(HitBands &b, const RenderMaterial *mat, const SampleRecs &rec, int slot) {
+    load_spec(b.h, mat, rec, slot);
+    b.r_lo = INFINITY;
+    b.r_hi = 0.f;
+    b.r_nonneg = 1;
+    bool black = true;
+#pragma unroll
+    for (int c = 0; c < NB; ++c) {
+        const float r = mat ? b.h.R(c) : 0.f;  // (a light sphere's matte lobe reads no R)
+        b.Rv[c] = r;
+        if (!(r >= 0.f)) b.r_nonneg = 0;
+        if (r > 0.f) b.r_lo = fminf(b.r_lo, r);
+        b.r_hi = fmaxf(b.r_hi, r);
+        black = black && r == 0.f;
+    }
+    if (black) b.r_lo = 0.f;
+}
+
 // ld[c] = sum over lights of (sum over j of (0 + light term + BSDF term)) / ns, band by band in
 // the order UniformSampleAllLights accumulates (Ld += EstimateDirect; L += Ld / nSamples). Each
 // light sample's record is read once and added to all 30 per-band accumulators (registers);
 // every band sees exactly the reference's sequence of float operations. kInf: the scene has
 // infinite lights, whose radiance depends on each term's direction (map coordinates in inf_st).
-template <bool kInf>
-__global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, SampleRecs rec, int max_hits, int ns_max,
-                                                             const DirectTerms *__restrict__ terms,
-                                                             const float4 *__restrict__ inf_st) {
+// kSpec: R and T are the hit's own (HitBands) -- direct_combine_spec_kernel.
+template <bool kInf, bool kSpec>
+__device__ __forceinline__ void direct_combine(const RenderScene &sc, const SampleRecs &rec, int max_hits, int ns_max,
+                                               const DirectTerms *__restrict__ terms,
+                                               const float4 *__restrict__ inf_st) {
     const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int nhits = *rec.hit_count;
     if (slot >= nhits || slot >= max_hits) return;
@@ -371,6 +494,8 @@ __global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, Sam
     if ((hs & HS_LIGHT) && !(hs & HS_LSURF)) return;
     // a light sphere's surface: the matte lobe (kind 3) needs no material
     const RenderMaterial *mat = (hs & HS_LIGHT) ? nullptr : &sc.materials[(hs >> REC_MAT_SHIFT) & 0xffu];
+    std::conditional_t<kSpec, HitBands, MatBands> bd;
+    load_bands(bd, mat, rec, slot);
     const size_t base = (size_t)slot * sc.nlights * ns_max;
     float ld[NB];
 #pragma unroll
@@ -392,12 +517,12 @@ __global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, Sam
                 inf_lookup(L, st.z, st.w, rgb2);
             }
             const Den d1 = make_den(e.l1.d), d2 = make_den(e.l2.d), dp = make_den(e.pdf2);
-            if (!e.l2.kind && e.l1.kind == 1u && refl_quotients_safe(*mat, e.l1, d1)) {
+            if (!e.l2.kind && e.l1.kind == 1u && refl_quotients_safe(bd.range(), e.l1, d1)) {
                 // the common term: a Microfacet light-sample half alone, its quotients on the fast path
 #pragma unroll
                 for (int c = 0; c < NB; ++c) {
                     const float Li1 = inf ? illum_band(rgb1, c) : L.Lemit[c];
-                    const float x = mat->R[c] * e.l1.a * e.l1.b * e.l1.c;
+                    const float x = bd.R(c) * e.l1.a * e.l1.b * e.l1.c;
                     const float q = x * d1.inv;
                     const float f1 = __builtin_fmaf(__builtin_fmaf(-d1.d, q, x), d1.inv, q);
                     Ld[c] += 0.f + f1 * Li1 * e.k1;
@@ -409,8 +534,8 @@ __global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, Sam
                 const float Li1 = inf ? illum_band(rgb1, c) : L.Lemit[c];
                 const float Li2 = inf ? illum_band(rgb2, c) : L.Lemit[c];
                 float ed = 0.f;
-                if (e.l1.kind) ed += lobe_value_den(mat, e.l1, c, d1) * Li1 * e.k1;
-                if (e.l2.kind) ed += div_by(lobe_value_den(mat, e.l2, c, d2) * Li2 * e.adn * e.w2, dp.d, dp.inv, dp.ok);
+                if (e.l1.kind) ed += lobe_value_den(bd, e.l1, c, d1) * Li1 * e.k1;
+                if (e.l2.kind) ed += div_by(lobe_value_den(bd, e.l2, c, d2) * Li2 * e.adn * e.w2, dp.d, dp.inv, dp.ok);
                 Ld[c] += ed;
             }
         }
@@ -431,9 +556,25 @@ __global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, Sam
     for (int k = 0; k < 7; ++k) row[k] = make_float4(ld[4 * k], ld[4 * k + 1], ld[4 * k + 2], ld[4 * k + 3]);
     row[7] = make_float4(ld[28], ld[29], 0.f, 0.f);
 }
+template <bool kInf>
+__global__ __launch_bounds__(256) void direct_combine_kernel(RenderScene sc, SampleRecs rec, int max_hits, int ns_max,
+                                                             const DirectTerms *__restrict__ terms,
+                                                             const float4 *__restrict__ inf_st) {
+    direct_combine<kInf, false>(sc, rec, max_hits, ns_max, terms, inf_st);
+}
+template <bool kInf>
+__global__ __launch_bounds__(256) void direct_combine_spec_kernel(RenderScene sc, SampleRecs rec, int max_hits,
+                                                                  int ns_max, const DirectTerms *__restrict__ terms,
+                                                                  const float4 *__restrict__ inf_st) {
+    direct_combine<kInf, true>(sc, rec, max_hits, ns_max, terms, inf_st);
+}
 template __global__ void direct_combine_kernel<false>(RenderScene, SampleRecs, int, int, const DirectTerms *,
                                                       const float4 *);
 template __global__ void direct_combine_kernel<true>(RenderScene, SampleRecs, int, int, const DirectTerms *,
                                                      const float4 *);
+template __global__ void direct_combine_spec_kernel<false>(RenderScene, SampleRecs, int, int, const DirectTerms *,
+                                                           const float4 *);
+template __global__ void direct_combine_spec_kernel<true>(RenderScene, SampleRecs, int, int, const DirectTerms *,
+                                                          const float4 *);
 
 }  // namespace mpss

@@ -6,6 +6,7 @@
 #include "../../data/spectral_bands.h"
 #include "common.h"
 #include "pbrt_math.h"
+#include "texture.h"
 
 namespace mpss {
 namespace {
@@ -61,7 +62,9 @@ __device__ __forceinline__ float illum_band(const float rgb[3], int c) {
     return v < 0.f ? 0.f : v;  // Clamp(0, INFINITY)
 }
 
-// band c of Spectrum::FromRGB(rgb) (reflectance; spectrum.cpp:103-187): ImageTexture's convertOut
+// band c of Spectrum::FromRGB(rgb) (reflectance; spectrum.cpp:103-187): ImageTexture's convertOut.
+// Its six cases stand three times in this file: here, in tex_albedo_pow_all and in refl_split (with
+// refl_split_band). A change to the rows or the order of one is a change to all three.
 __device__ __forceinline__ float refl_band(const float rgb[3], int c) {
     const float R = rgb[0], G = rgb[1], B = rgb[2];
     float r = 0.f;
@@ -111,7 +114,7 @@ __device__ __forceinline__ float tex_albedo_pow(const float rgb[3], int c, float
 // spectrum.cpp:103-187) decided once per lane instead of per band: the minimum / middle / maximum
 // components and the rows of their secondary (X: Cyan, Magenta, Yellow) and primary (Y: Red, Green,
 // Blue) spectra; then per band the same products and sums in the same order. e = 0.5 (the default mix)
-// as sqrtf (tex_albedo_pow).
+// as sqrtf (tex_albedo_pow). (The case table is refl_band's and refl_split's: keep the three alike.)
 __device__ __forceinline__ void tex_albedo_pow_all(const float4 rgb, float e, float out[NB]) {
     const float R = rgb.x, G = rgb.y, B = rgb.z;
     float mn, md, mx;
@@ -142,6 +145,56 @@ __device__ __forceinline__ void tex_albedo_pow_all(const float4 rgb, float e, fl
         v = v < 0.f ? 0.f : v;
         out[c] = e == 0.5f ? __builtin_sqrtf(v) : tex_pow_general(v, e);
     }
+}
+
+// FromRGB(rgb) (reflectance) with refl_band's branches decided once, for a spectrum that is read band by
+// band later (a hit's Kr / Kt texture lookup, shade.hip): the minimum component, the two differences and
+// the rows of the secondary and primary spectra, as tex_albedo_pow_all picks them; refl_split_band(s, c)
+// is refl_band(rgb, c) -- the same products and sums in the same order. (The case table is refl_band's
+// and tex_albedo_pow_all's: keep the three alike; test_spec_texture_gpu's block textures hold this copy
+// to the oracle's FromRGB in each of its colours' cases.)
+struct ReflSplit {
+    float mn, d1, d2;
+    int xi, yi;
+};
+__device__ __forceinline__ ReflSplit refl_split(float R, float G, float B) {
+    float mn, md, mx;
+    int xi, yi;
+    if (R <= G && R <= B) {
+        mn = R;
+        xi = 1;
+        if (G <= B) { md = G; mx = B; yi = 6; } else { md = B; mx = G; yi = 5; }
+    } else if (G <= R && G <= B) {
+        mn = G;
+        xi = 2;
+        if (R <= B) { md = R; mx = B; yi = 6; } else { md = B; mx = R; yi = 4; }
+    } else {
+        mn = B;
+        xi = 3;
+        if (R <= G) { md = R; mx = G; yi = 5; } else { md = G; mx = R; yi = 4; }
+    }
+    return ReflSplit{mn, md - mn, mx - md, xi, yi};
+}
+__device__ __forceinline__ float refl_split_band(const ReflSplit &s, int c) {
+    const float X = s.xi == 1 ? kRefl[1][c] : (s.xi == 2 ? kRefl[2][c] : kRefl[3][c]);
+    const float Y = s.yi == 4 ? kRefl[4][c] : (s.yi == 5 ? kRefl[5][c] : kRefl[6][c]);
+    float r = 0.f;
+    r += kRefl[0][c] * s.mn;
+    r += X * s.d1;
+    r += Y * s.d2;
+    const float v = r * .94f;
+    return v < 0.f ? 0.f : v;
+}
+
+// A hit's Kr / Kt record (SampleRecs::hit_kr, hit_kt): the texture's RGB at the hit's shading geometry and,
+// in w, whether FromRGB of it has a nonzero band (!Spectrum::IsBlack(): 1, else 0)
+__device__ __forceinline__ float4 spec_lookup(const TexView &T, const UVDiff &g) {
+    float rgb[3];
+    tex_eval(T, g, rgb);
+    const ReflSplit s = refl_split(rgb[0], rgb[1], rgb[2]);
+    bool black = true;
+    for (int c = 0; c < NB; ++c) black = black && refl_split_band(s, c) == 0.f;
+    return make_float4(rgb[0], rgb[1], rgb[2], black ? 0.f : 1.f);
 }
 
 __device__ __forceinline__ float rho_lookup(const float *hd, int n, float ct) {  // multipole.cpp:458-463

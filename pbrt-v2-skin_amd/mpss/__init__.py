@@ -154,6 +154,7 @@ _sig("mpss_host_tessellate", C.c_int, [u32, f32p, vp, vp, vp, u32, C.POINTER(C.c
 _sig("mpss_imagemap_defaults", None, [C.POINTER(Imagemap)])
 _sig("mpss_add_imagemap", C.c_int, [vp, C.POINTER(Imagemap), u32p])
 _sig("mpss_set_material_textures", C.c_int, [vp, u32, C.c_int32, C.c_int32])
+_sig("mpss_set_material_spec_textures", C.c_int, [vp, u32, C.c_int32, C.c_int32])
 _sig("mpss_host_tessellate_bumped", C.c_int, [u32, f32p, vp, vp, vp, u32, C.POINTER(C.c_int32), f32p, f32p, C.c_int,
                                               u32, C.c_float, C.c_int, vp, vp, u32p])
 _sig("mpss_host_imagemap_lookup", C.c_int, [C.POINTER(Imagemap), u32, f32p, f32p])
@@ -705,6 +706,11 @@ class Context:
 
     def set_material_textures(self, material, albedo=-1, bump=-1):
         check(_lib.mpss_set_material_textures(self.h, material, albedo, bump))
+
+    def set_material_spec_textures(self, material, kr=-1, kt=-1):
+        """LayeredSkin's "texture Kr" / "texture Kt": spectrum imagemap ids evaluated per camera hit
+        (-1: the material's constant Kr / Kt)."""
+        check(_lib.mpss_set_material_spec_textures(self.h, material, kr, kt))
 
     def add_sphere_light(self, center, radius, Lemit, nsamples=1):
         check(_lib.mpss_add_sphere_light(self.h, np.ascontiguousarray(center, np.float32), radius,

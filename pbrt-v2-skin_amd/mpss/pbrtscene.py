@@ -371,11 +371,8 @@ def _skin_params(ps, textures):
                 t = textures[vals[0]]
                 if t["type"] == "float":
                     raise ValueError("%s needs a spectrum texture, %r is a float texture" % (k, vals[0]))
-                if t["cls"] == "imagemap":
-                    if k != "albedo":
-                        raise ValueError("an imagemap %s is outside this path (DESIGN.md); albedo and bumpmap "
-                                         "take image textures" % k)
-                    p["albedo_tex"] = t["tex"]
+                if t["cls"] == "imagemap":  # albedo_tex; kr_tex / kt_tex (evaluated per camera hit)
+                    p[k.lower() + "_tex"] = t["tex"]
                     continue
                 vals = t["value"]
             p[k] = _rgb3(vals)
@@ -522,10 +519,14 @@ def infinite_texels(li):
     return imageio.read_image(li["mapname"])
 
 
+# a material dict's texture bindings (mpss.imagemap keyword dicts): not fields of mpss_layeredskin
+TEXTURE_KEYS = ("albedo_tex", "bump_tex", "kr_tex", "kt_tex")
+
+
 def skin_struct(m):
     """The mpss_layeredskin of one of a Scene's material dicts (its texture bindings aside)."""
     import mpss
-    kw = {k: v for k, v in m.items() if k not in ("Kr", "Kt", "albedo", "albedo_tex", "bump_tex")}
+    kw = {k: v for k, v in m.items() if k not in ("Kr", "Kt", "albedo") + TEXTURE_KEYS}
     for k in ("Kr", "Kt", "albedo"):
         if k in m:
             kw[k] = mpss.host_from_rgb(m[k])
@@ -552,6 +553,10 @@ def build_context(sc, timings=None, grid_on_host=None, **cfg_kw):
             alb = ctx.add_imagemap(**m["albedo_tex"]) if m.get("albedo_tex") is not None else -1
             bump = ctx.add_imagemap(**m["bump_tex"]) if m.get("bump_tex") is not None else -1
             ctx.set_material_textures(mid, alb, bump)
+        if m.get("kr_tex") is not None or m.get("kt_tex") is not None:
+            kr = ctx.add_imagemap(**m["kr_tex"]) if m.get("kr_tex") is not None else -1
+            kt = ctx.add_imagemap(**m["kt_tex"]) if m.get("kt_tex") is not None else -1
+            ctx.set_material_spec_textures(mid, kr, kt)
     for me in sc.meshes:
         ctx.add_mesh(me["P"], me["indices"], me["o2w"], me["w2o"], mids[me["material"]], N=me["N"], S=me["S"],
                      uv=me["uv"], reverse=me["reverse"])
