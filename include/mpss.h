@@ -343,6 +343,22 @@ int mpss_render_tile(mpss_ctx *ctx, int spp, uint32_t seed, int x0, int x1, int 
  * mpss_render_tile calls. */
 int mpss_render_tiles(mpss_ctx *ctx, int spp, uint32_t seed, int n, const int32_t *rects, float *const *xyzw_dev,
                       void *stream);
+/* The spectral film: the radiance of the 30 bands, before Spectrum::ToXYZ folds them into X, Y, Z.
+ * As mpss_render_tile(s); spec_dev (spec_dev[i]; 16-byte aligned, device memory) receives (y1-y0)*(x1-x0) rows of
+ * MPSS_SPECTRAL_ROW floats: [c] = the sum over the samples the pixel filter carries into the pixel of
+ * w * L_c for band c < MPSS_NBANDS, [30] = the sum of w, [31] = 0. L is what the integrator hands to
+ * AddSample (Le + the clamped subsurface term + Ld, or the infinite lights' Le for an escaped ray); a sample
+ * that SamplerRenderer's filter rejects from its XYZ (NaN, y < -1e-5, infinite y) has L = 0 in every band and
+ * its weight still counts. Weights, samples and their order are the XYZW film's, band by band: [30] has
+ * the bits of that film's W, mpss_host_spectrum_to_xyz of [0..29] is its XYZ up to the order of the float sums,
+ * and a frame is the same bit for bit however it is cut into tiles (hash sampler).
+ * xyzw_dev (or any xyzw_dev[i]) may be NULL; when given it receives exactly what mpss_render_tile(s) writes.
+ * A NULL spec_dev or spec_dev[i]: MPSS_ERR_INVALID, before anything is launched. */
+#define MPSS_SPECTRAL_ROW 32
+int mpss_render_tile_spectral(mpss_ctx *ctx, int spp, uint32_t seed, int x0, int x1, int y0, int y1, float *spec_dev,
+                              float *xyzw_dev, void *stream);
+int mpss_render_tiles_spectral(mpss_ctx *ctx, int spp, uint32_t seed, int n, const int32_t *rects,
+                               float *const *spec_dev, float *const *xyzw_dev, void *stream);
 
 /* Cost probe for dealing tiles to GPUs (the bench's multi-GPU path; not a reference entry point):
  * one camera ray through the centre of every pixel, counted per rectangle (rects[4*i..] = x0, x1,
@@ -499,6 +515,10 @@ int mpss_sog_fit(mpss_ctx *ctx, uint32_t n_profiles, uint32_t length, const floa
 /* SampledSpectrum::FromRGB (spectrum.cpp:103-187); pbrt's "color"/"rgb" parameters use
  * illuminant = 0 (ParamSet::AddRGBSpectrum, paramset.cpp:97-105). */
 int mpss_host_from_rgb(const float *rgb, int illuminant, float *out);
+/* Spectrum::ToXYZ (spectrum.h:374-386) of n spectra of MPSS_NBANDS floats -> n x {X, Y, Z}: the sums in band
+ * order, then the scale, as the film's Li assembly computes a sample's XYZ. No sample filter is applied (a NaN
+ * band gives NaN). */
+int mpss_host_spectrum_to_xyz(const float *spec, uint32_t n, float *xyz);
 /* TessellateSurfacePoints of one triangle mesh (trianglemesh.cpp:187-351); flip =
  * ReverseOrientation ^ ObjectToWorld.SwapsHandedness(). Sizes first with records NULL. */
 int mpss_host_tessellate(uint32_t nverts, const float *P, const float *N, const float *S, const float *uv,

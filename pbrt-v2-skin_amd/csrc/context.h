@@ -158,7 +158,10 @@ public:
     void tessellate_on_gpu();  // Preprocess point set, GPU build (preprocess_host.hip)
     // FindPoissonPointDistribution (usepoissonpointfinder): fills points_ (preprocess_host.hip)
     void find_poisson_points(uint32_t seed);
-    void render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, float *const *outs, hipStream_t stream);
+    // spec (mpss_render_tiles_spectral): per rectangle, its rows of MPSS_SPECTRAL_ROW floats per pixel; outs,
+    // or any outs[i], may then be null (no XYZW film for that rectangle)
+    void render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, float *const *outs, hipStream_t stream,
+                      float *const *spec = nullptr);
     // the replay sampler's table (mpss_replay_samples); out may be null to query sizes
     void replay_samples(int spp, float *out, uint64_t *n_floats, int *k);
     void check_replay_lds(int spp, const char *who) const;  // replay_check_lds over the scene's lights
@@ -266,6 +269,7 @@ private:
     void batch_direct(TileCall &c, const RenderScene &sc, int64_t nh);
     void batch_mo(TileCall &c, int64_t nh);
     void batch_film(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, int64_t nh);
+    void launch_films_spectral(const TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b);
     SceneData scene_;
     bool scene_dirty_ = true, materials_dirty_ = false;
     // where points_ came from: the caller (set_surface_points / pointsfile) or a Preprocess of this

@@ -4,6 +4,9 @@
 //   sky_kernel       the same for camera rays that escaped to infinite lights (samplerrenderer.cpp:144-151)
 //   film_kernel      ImageFilm::AddSample with the 0.5-wide box filter (film/image.cpp:77-137)
 //   film_filter_kernel  ... with any other filter, through ImageFilm's weight table (pixel_filter.h)
+// A spectral call (mpss_render_tile_spectral) runs the <true> instances of the first two, which also leave the
+// sample's 30-band L in the hit's own Ld row (zeros for a sample the filter rejects); the films over those
+// rows are film_spectral.hip's.
 #include "render.h"
 
 #include "film_filter.h"
@@ -22,7 +25,7 @@ namespace mpss {
 // wave-uniform (its tables are scalar loads), the lane's Ld row and the band-ordered Mo() values
 // are all issued up front, and the 30-band loop is unrolled -- the same float operations, in the
 // same order, as the general path below.
-template <bool TEX>
+template <bool TEX, bool SPEC>
 __device__ __forceinline__ void assemble_uniform(const RenderScene &sc, const SampleRecs &rec, int slot, int mid) {
     const RenderMaterial &mat = sc.materials[mid];
     const float4 q = rec.hit_q[slot];
@@ -61,6 +64,7 @@ __device__ __forceinline__ void assemble_uniform(const RenderScene &sc, const Sa
         X += kCieX[c] * L;
         Y += kCieY[c] * L;
         Z += kCieZ[c] * L;
+        if (SPEC) ld[c] = L;
     }
     const float scale = (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
     const float y = Y * (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
@@ -69,8 +73,18 @@ __device__ __forceinline__ void assemble_uniform(const RenderScene &sc, const Sa
     Z *= scale;
     if (nan || y < -1e-5f || __builtin_isinf(y)) X = Y = Z = 0.f;
     rec.xyz[slot] = make_float4(X, Y, Z, 0.f);
+    if (SPEC) {  // the sample's L over its Ld row (read above), 0 for a rejected sample
+        const bool rej = nan || y < -1e-5f || __builtin_isinf(y);
+        float4 *row = reinterpret_cast<float4 *>(rec.ld + (size_t)slot * ROW);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            row[k] = rej ? make_float4(0.f, 0.f, 0.f, 0.f)
+                         : make_float4(ld[4 * k], ld[4 * k + 1], ld[4 * k + 2], ld[4 * k + 3]);
+    }
 }
 
+// SPEC (a spectral call): the sample's L also goes over the hit's Ld row, 0 for a rejected sample
+template <bool SPEC>
 __global__ __launch_bounds__(256) void assemble_kernel(RenderScene sc, SampleRecs rec, int max_hits) {
     const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int nhits = *rec.hit_count;
@@ -84,9 +98,9 @@ __global__ __launch_bounds__(256) void assemble_kernel(RenderScene sc, SampleRec
         if (__builtin_amdgcn_ballot_w64(in && !fast) == 0) {
             if (in) {
                 if (sc.materials[mid0].has_alb_tex)
-                    assemble_uniform<true>(sc, rec, slot, mid0);
+                    assemble_uniform<true, SPEC>(sc, rec, slot, mid0);
                 else
-                    assemble_uniform<false>(sc, rec, slot, mid0);
+                    assemble_uniform<false, SPEC>(sc, rec, slot, mid0);
             }
             return;
         }
@@ -134,6 +148,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(RenderScene sc, SampleRec
         X += kCieX[c] * L;
         Y += kCieY[c] * L;
         Z += kCieZ[c] * L;
+        if (SPEC) rec.ld[(size_t)slot * ROW + c] = L;  // (band c of the row is read above)
     }
     const float scale = (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
     const float y = Y * (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
@@ -142,12 +157,17 @@ __global__ __launch_bounds__(256) void assemble_kernel(RenderScene sc, SampleRec
     Z *= scale;
     if (nan || y < -1e-5f || __builtin_isinf(y)) X = Y = Z = 0.f;
     rec.xyz[slot] = make_float4(X, Y, Z, 0.f);
+    if (SPEC && (nan || y < -1e-5f || __builtin_isinf(y)))
+        for (int c = 0; c < NB; ++c) rec.ld[(size_t)slot * ROW + c] = 0.f;
 }
+template __global__ void assemble_kernel<false>(RenderScene sc, SampleRecs rec, int max_hits);
+template __global__ void assemble_kernel<true>(RenderScene sc, SampleRecs rec, int max_hits);
 
 // Camera rays that escaped with infinite lights in the scene (SamplerRenderer::Li,
 // samplerrenderer.cpp:144-151): L = 0 + sum over lights of Le(ray), area lights adding 0; then
 // the sample filter and ToXYZ as in assemble_kernel. A separate launch keeps assemble_kernel's
 // registers (and occupancy) independent of the 30-band sky sum.
+template <bool SPEC>
 __global__ __launch_bounds__(256) void sky_kernel(RenderScene sc, SampleRecs rec, int max_hits) {
     const int slot = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int nhits = *rec.hit_count;
@@ -184,7 +204,18 @@ __global__ __launch_bounds__(256) void sky_kernel(RenderScene sc, SampleRecs rec
     Z *= scale;
     if (nan || y < -1e-5f || __builtin_isinf(y)) X = Y = Z = 0.f;
     rec.xyz[slot] = make_float4(X, Y, Z, 0.f);
+    if (SPEC) {  // an escaped ray has an Ld row of its own like every slot: nothing else uses it
+        const bool rej = nan || y < -1e-5f || __builtin_isinf(y);
+        float4 *row = reinterpret_cast<float4 *>(rec.ld + (size_t)slot * ROW);
+#pragma unroll
+        for (int k = 0; k < 7; ++k)
+            row[k] = rej ? make_float4(0.f, 0.f, 0.f, 0.f)
+                         : make_float4(Ls[4 * k], Ls[4 * k + 1], Ls[4 * k + 2], Ls[4 * k + 3]);
+        row[7] = rej ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(Ls[28], Ls[29], 0.f, 0.f);
+    }
 }
+template __global__ void sky_kernel<false>(RenderScene sc, SampleRecs rec, int max_hits);
+template __global__ void sky_kernel<true>(RenderScene sc, SampleRecs rec, int max_hits);
 
 __global__ __launch_bounds__(256) void film_kernel(RenderScene sc, PieceList pl, SampleRecs rec) {
     const int k = piece_of(pl, (int)blockIdx.x);

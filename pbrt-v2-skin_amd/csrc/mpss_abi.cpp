@@ -518,6 +518,25 @@ int mpss_render_tiles(mpss_ctx *c, int spp, uint32_t seed, int n, const int32_t 
     });
 }
 
+int mpss_render_tile_spectral(mpss_ctx *c, int spp, uint32_t seed, int x0, int x1, int y0, int y1, float *spec,
+                              float *out, void *stream) {
+    return guarded([&] {
+        require(c && spec, "mpss_render_tile_spectral: null argument");
+        const int32_t r[4] = {x0, x1, y0, y1};
+        float *o[1] = {out}, *s[1] = {spec};
+        reinterpret_cast<Context *>(c)->render_tiles(spp, seed, 1, r, o, (hipStream_t)stream, s);
+    });
+}
+
+int mpss_render_tiles_spectral(mpss_ctx *c, int spp, uint32_t seed, int n, const int32_t *rects, float *const *specs,
+                               float *const *outs, void *stream) {
+    return guarded([&] {
+        require(c && n >= 0 && (n == 0 || (rects && specs)), "mpss_render_tiles_spectral: null argument");
+        if (n == 0) specs = outs = nullptr;  // nothing to render: an XYZ call over no rectangles
+        reinterpret_cast<Context *>(c)->render_tiles(spp, seed, n, rects, outs, (hipStream_t)stream, specs);
+    });
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------- host-side utilities
@@ -654,6 +673,13 @@ int mpss_host_from_rgb(const float *rgb, int illuminant, float *out) {
     return guarded([&] {
         require(rgb && out, "mpss_host_from_rgb: null argument");
         spectrum_from_rgb(rgb, illuminant != 0, out);
+    });
+}
+
+int mpss_host_spectrum_to_xyz(const float *spec, uint32_t n, float *xyz) {
+    return guarded([&] {
+        require(n == 0 || (spec && xyz), "mpss_host_spectrum_to_xyz: null argument");
+        for (uint32_t i = 0; i < n; ++i) spectrum_to_xyz(spec + (size_t)i * NB, xyz + (size_t)i * 3);
     });
 }
 

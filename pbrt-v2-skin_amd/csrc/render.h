@@ -229,11 +229,15 @@ __global__ void shade_nolight_kernel(RenderScene sc, SampleRecs rec, int max_hit
 template <bool kInf>
 __global__ void direct_combine_kernel(RenderScene sc, SampleRecs rec, int max_hits, int ns_max,
                                       const DirectTerms *terms, const float4 *inf_st);
-// Li assembly per slot (L = Le + SSS + Ld, sample filter, ToXYZ), then the box-filtered film.
+// Li assembly per slot (L = Le + SSS + Ld, sample filter, ToXYZ), then the box-filtered film. SPEC (a
+// spectral call, film_spectral.h): the sample's 30-band L also goes over the slot's Ld row, zeros for a
+// sample the filter rejects. (film.hip instantiates both.)
+template <bool SPEC>
 __global__ void assemble_kernel(RenderScene sc, SampleRecs rec, int max_hits);
 // Tile-cost probe: one camera ray through the centre of every pixel of [x0, x1) x [y0, y1);
 // cls[i] = 0 miss or light, 1 mesh surface, 2 BSSRDF surface (render_host.hip tile_costs).
 __global__ void probe_kernel(RenderScene sc, int x0, int x1, int y0, int y1, uint8_t *cls);
+template <bool SPEC>
 __global__ void sky_kernel(RenderScene sc, SampleRecs rec, int max_hits);
 __global__ void film_kernel(RenderScene sc, PieceList pl, SampleRecs rec0);
 

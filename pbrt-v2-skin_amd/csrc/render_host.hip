@@ -7,6 +7,7 @@
 
 #include "context.h"
 #include "film_filter.h"
+#include "film_spectral.h"
 #include "render.h"
 
 namespace mpss {
@@ -96,6 +97,9 @@ struct Context::TileCall {
     hipStream_t stream;
     RenderWorkspace *ws;
     float *const *outs;  // per rectangle
+    // a spectral call (mpss_render_tile(s)_spectral): per rectangle, rows of ROW floats per pixel; outs, or
+    // outs[i], may then be null. Null: an XYZ call.
+    float *const *spec;
     int spp;
     uint32_t seed;
     int nlights, ns_max;
@@ -162,7 +166,8 @@ void Context::launch_pieces(const TileCall &c, const RenderScene &sc, const Tile
             pl.block0[j] = g.block0[j];
             pl.tb[j] = p.tb;
             pl.off[j] = g.off[j];
-            pl.out[j] = c.outs[p.rect] + p.out_off;
+            float *const o = c.outs[p.rect];  // (null: a spectral call's rectangle without an XYZW output)
+            pl.out[j] = o ? o + p.out_off : nullptr;
             pl.out_stride[j] = g.out_stride[j];
         }
         pl.block0[g.n] = g.blocks;
@@ -286,14 +291,62 @@ void Context::batch_mo(TileCall &c, int64_t nh) {
     time_end(c.timing, c.stream, ev, 2, c.timed);
 }
 
+// A spectral call's films over the batch's pieces: the band film into every piece's rows of the cube, and
+// the XYZ film (the kernels of an XYZ call) into the pieces of rectangles that have an XYZW output. The launch
+// groups are launch_pieces'; the band films' workgroups hold 256 / kSpecLanes pixels.
+void Context::launch_films_spectral(const TileCall &c, const RenderScene &sc, const TilePlan &plan,
+                                    const PlanBatch &b) {
+    static_assert(ROW == MPSS_SPECTRAL_ROW, "a cube row is a hit's Ld row");
+    for (const LaunchGroup &g : launch_groups(plan, b, true, c.filtered ? kFilmTile : 0)) {
+        PieceList xyz{}, sp{};
+        xyz.n = sp.n = g.n;
+        int nx = 0, ns = 0;
+        for (int j = 0; j < g.n; ++j) {
+            const PlanPiece &p = plan.pieces[g.first + j];
+            const int tw = p.tb.x1 - p.tb.x0, th = p.tb.y1 - p.tb.y0;
+            float *const o = c.outs[p.rect];
+            xyz.block0[j] = nx;
+            sp.block0[j] = ns;
+            xyz.tb[j] = sp.tb[j] = p.tb;
+            xyz.off[j] = sp.off[j] = g.off[j];
+            xyz.out_stride[j] = sp.out_stride[j] = g.out_stride[j];
+            xyz.out[j] = o ? o + p.out_off : nullptr;  // (no XYZW output: no blocks)
+            sp.out[j] = c.spec[p.rect] + p.out_off * (ROW / 4);
+            if (o) nx += g.block0[j + 1] - g.block0[j];
+            ns += c.filtered ? ((tw + kSpecTileX - 1) / kSpecTileX) * ((th + kSpecTileY - 1) / kSpecTileY)
+                             : (int)(((int64_t)tw * th * kSpecLanes + 255) / 256);
+        }
+        xyz.block0[g.n] = nx;
+        sp.block0[g.n] = ns;
+        if (c.filtered) {
+            hipLaunchKernelGGL(film_filter_spectral_kernel, dim3((unsigned)ns), dim3(256), 0, c.stream, sc, sp,
+                               c.recs(), c.ff);
+            if (nx > 0)
+                hipLaunchKernelGGL(film_filter_kernel, dim3((unsigned)nx), dim3(256), 0, c.stream, sc, xyz, c.recs(),
+                                   c.ff);
+        } else {
+            hipLaunchKernelGGL(film_spectral_kernel, dim3((unsigned)ns), dim3(256), 0, c.stream, sc, sp, c.recs());
+            if (nx > 0) hipLaunchKernelGGL(film_kernel, dim3((unsigned)nx), dim3(256), 0, c.stream, sc, xyz, c.recs());
+        }
+    }
+}
+
 // Li assembly per hit, the sky behind the misses, then the filtered film per piece
 void Context::batch_film(TileCall &c, const RenderScene &sc, const TilePlan &plan, const PlanBatch &b, int64_t nh) {
     const SampleRecs rec = c.recs();
     const dim3 per_hit((unsigned)((nh + 255) / 256));
     hipEvent_t ev{};
     time_begin(c.timing, c.stream, ev);
-    hipLaunchKernelGGL(assemble_kernel, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
-    if (sc.n_infinite > 0) hipLaunchKernelGGL(sky_kernel, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+    if (c.spec) {
+        hipLaunchKernelGGL(assemble_kernel<true>, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+        if (sc.n_infinite > 0) hipLaunchKernelGGL(sky_kernel<true>, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+        launch_films_spectral(c, sc, plan, b);
+        time_end(c.timing, c.stream, ev, 3, c.timed);
+        MPSS_HIP(hipGetLastError());
+        return;
+    }
+    hipLaunchKernelGGL(assemble_kernel<false>, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
+    if (sc.n_infinite > 0) hipLaunchKernelGGL(sky_kernel<false>, per_hit, dim3(256), 0, c.stream, sc, rec, (int)nh);
     launch_pieces(c, sc, plan, b, true);
     time_end(c.timing, c.stream, ev, 3, c.timed);
     MPSS_HIP(hipGetLastError());
@@ -307,7 +360,7 @@ void Context::batch_film(TileCall &c, const RenderScene &sc, const TilePlan &pla
 // over the pieces. Calls on different streams may overlap: each takes its own workspace (RenderWorkspace),
 // and the scene, materials and octree are only read after the context lock is released.
 void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, float *const *outs,
-                           hipStream_t stream) {
+                           hipStream_t stream, float *const *spec) {
     activate();
     std::unique_lock<std::mutex> lk(mu_);
     require_fresh_irradiance("render_tile");
@@ -326,13 +379,19 @@ void Context::render_tiles(int spp, uint32_t seed, int n, const int32_t *rects, 
             throw Error(MPSS_ERR_INVALID, "render_tile: the reference sampler renders only with the default pixel "
                                           "filter (box 0.5 / 0.5); set that filter or use the hash sampler");
     }
+    std::vector<float *> no_outs;  // a spectral call without XYZW outputs: a null one per rectangle
+    if (spec && !outs) {
+        no_outs.assign((size_t)std::max(n, 1), nullptr);
+        outs = no_outs.data();
+    }
     for (int i = 0; i < n; ++i) {
         if (!tile_rect_ok(rects + 4 * i, W, H)) throw Error(MPSS_ERR_INVALID, "render_tile: bad rectangle");
-        if (!outs[i]) throw Error(MPSS_ERR_INVALID, "render_tile: null output");
+        if (spec ? !spec[i] : !outs[i]) throw Error(MPSS_ERR_INVALID, "render_tile: null output");
     }
     TileCall c{};
     c.stream = stream;
     c.outs = outs;
+    c.spec = spec;
     c.spp = spp;
     c.seed = seed;
     c.filtered = !filter_.is_default();

@@ -26,6 +26,19 @@ inline float spectrum_y(const float *s) {
     return yy * (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
 }
 
+// SampledSpectrum::ToXYZ (spectrum.h:374-386): the sums in band order, then the scale -- the arithmetic of
+// assemble_kernel (film.hip) on a sample's L
+inline void spectrum_to_xyz(const float *s, float xyz[3]) {
+    xyz[0] = xyz[1] = xyz[2] = 0.f;
+    for (int i = 0; i < NB; ++i) {
+        xyz[0] += MPSS_BAND_CIE_X[i] * s[i];
+        xyz[1] += MPSS_BAND_CIE_Y[i] * s[i];
+        xyz[2] += MPSS_BAND_CIE_Z[i] * s[i];
+    }
+    const float scale = (float)(700 - 400) / (float)(MPSS_CIE_Y_INTEGRAL * NB);
+    for (int k = 0; k < 3; ++k) xyz[k] *= scale;
+}
+
 // SampledSpectrum::ToXYZ + XYZToRGB (spectrum.h:51-55, 370-393): ToRGBSpectrum's texel value
 inline void spectrum_to_rgb(const float *s, float rgb[3]) {
     float xyz[3] = {0.f, 0.f, 0.f};

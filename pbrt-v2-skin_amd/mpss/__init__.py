@@ -139,8 +139,12 @@ _sig("mpss_reset_render_stats", C.c_int, [vp])
 _sig("mpss_set_instrumentation", C.c_int, [vp, C.c_int, C.c_int])
 _sig("mpss_render_tile", C.c_int, [vp, C.c_int, u32, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp])
 _sig("mpss_render_tiles", C.c_int, [vp, C.c_int, u32, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp), vp])
+_sig("mpss_render_tile_spectral", C.c_int, [vp, C.c_int, u32, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp])
+_sig("mpss_render_tiles_spectral", C.c_int, [vp, C.c_int, u32, C.c_int, C.POINTER(C.c_int32), C.POINTER(vp),
+                                             C.POINTER(vp), vp])
 _sig("mpss_tile_costs", C.c_int, [vp, C.c_int, C.POINTER(C.c_int32), vp, vp])
 _sig("mpss_host_from_rgb", C.c_int, [f32p, C.c_int, f32p])
+_sig("mpss_host_spectrum_to_xyz", C.c_int, [f32p, u32, f32p])
 _sig("mpss_mc_reference", C.c_int, [f32p, C.c_int, C.c_float, C.c_int, C.c_int, vp, vp, C.POINTER(C.c_double),
                                     C.POINTER(C.c_double)])
 _sig("mpss_mc_profile", C.c_int, [vp, f32p, C.c_int, C.c_float, C.c_int, C.c_uint64, C.c_uint64, vp, vp,
@@ -264,6 +268,19 @@ assert SURFACE_POINT.itemsize == 44
 def host_from_rgb(rgb, illuminant=False):
     out = np.zeros(NB, np.float32)
     check(_lib.mpss_host_from_rgb(np.ascontiguousarray(rgb, np.float32), int(illuminant), out))
+    return out
+
+
+SPECTRAL_ROW = 32  # MPSS_SPECTRAL_ROW: 30 band sums, the weight sum, 0
+
+
+def host_spectrum_to_xyz(spec):
+    """Spectrum::ToXYZ in band order (mpss_host_spectrum_to_xyz): spec (..., 30) -> (..., 3) float32."""
+    spec = np.ascontiguousarray(spec, np.float32)
+    if spec.shape[-1] != NB:
+        raise ValueError("spectra must have %d bands" % NB)
+    out = np.zeros(spec.shape[:-1] + (3,), np.float32)
+    check(_lib.mpss_host_spectrum_to_xyz(spec.reshape(-1), spec.size // NB, out.reshape(-1)))
     return out
 
 
@@ -873,3 +890,17 @@ class Context:
         r = (C.c_int32 * (4 * n))(*[int(v) for rc in rects for v in rc])
         o = (vp * n)(*outs_dev)
         check(_lib.mpss_render_tiles(self.h, spp, seed, n, r, o, stream))
+
+    def render_tile_spectral(self, spp, seed, x0, x1, y0, y1, spec_dev, out_dev=None, stream=None):
+        """mpss_render_tile_spectral: spec_dev receives SPECTRAL_ROW floats per pixel (30 band sums, the weight
+        sum, 0); out_dev (optional) the XYZW tile render_tile writes."""
+        check(_lib.mpss_render_tile_spectral(self.h, spp, seed, x0, x1, y0, y1, spec_dev, out_dev, stream))
+
+    def render_tiles_spectral(self, spp, seed, rects, specs_dev, outs_dev=None, stream=None):
+        """rects: [(x0, x1, y0, y1)]; specs_dev: device pointers (SPECTRAL_ROW floats per pixel each);
+        outs_dev: None, or one XYZW device pointer (or None) per rectangle."""
+        n = len(rects)
+        r = (C.c_int32 * (4 * max(n, 1)))(*[int(v) for rc in rects for v in rc])
+        s = (vp * max(n, 1))(*specs_dev)
+        o = None if outs_dev is None else (vp * max(n, 1))(*outs_dev)
+        check(_lib.mpss_render_tiles_spectral(self.h, spp, seed, n, r, s, o, stream))

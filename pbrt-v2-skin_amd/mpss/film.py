@@ -119,15 +119,61 @@ def write_exr(path, rgb, total_res=None, offset=(0, 0), compression="zip"):
     """WriteImageEXR: scanline HALF A/B/G/R (alpha 1), ZIP (16 lines a block) or NONE."""
     rgb = np.asarray(rgb, np.float32)
     h, w, _ = rgb.shape
+    with np.errstate(over="ignore"):
+        half = rgb.astype(np.float16)  # Rgba(float): round to nearest even, overflow to inf
+    alpha = np.ones((h, w), np.float16)
+    _write_exr_planes(path, [("A", alpha), ("B", half[..., 2]), ("G", half[..., 1]), ("R", half[..., 0])],
+                      total_res, offset, compression)
+
+
+def band_centres():
+    """The centres of the 30 bands in nm: 405, 415, ..., 695 (band c covers 400 + 10 c .. 410 + 10 c nm,
+    spectrum.h:46-48)."""
+    return [405 + 10 * c for c in range(30)]
+
+
+def spectral_channel_names():
+    """The cube's EXR channels in band order: S0.405nm ... S0.695nm (alphabetical, as the format stores them)."""
+    return ["S0.%dnm" % nm for nm in band_centres()]
+
+
+def finalize_spectral(spec):
+    """spec: [H, W, 32] float32 as mpss_render_tile_spectral writes it (30 band sums, the weight sum, 0) ->
+    the [H, W, 30] cube of band radiances: for a non-zero weight sum the band sums times 1 / weightSum,
+    finalize()'s rule without the colour transform and its clamp; a pixel without weight keeps its sums (0)."""
+    spec = np.asarray(spec, np.float32)
+    w = spec[..., 30:31]
+    safe = np.where(w != 0, w, np.float32(1))
+    inv = (np.float32(1) / safe).astype(np.float32)
+    return np.where(w != 0, (spec[..., :30] * inv).astype(np.float32), spec[..., :30]).astype(np.float32)
+
+
+def write_spectral_exr(path, cube, total_res=None, offset=(0, 0), compression="zip"):
+    """The [H, W, 30] cube as a scanline file of 30 FLOAT channels S0.<centre>nm (read it back with
+    imageio.read_exr_channels); header and ZIP blocks as write_exr's."""
+    cube = np.asarray(cube, np.float32)
+    if cube.ndim != 3 or cube.shape[2] != 30:
+        raise ValueError("cube must be (height, width, 30)")
+    _write_exr_planes(path, [(nm, cube[..., c]) for c, nm in enumerate(spectral_channel_names())], total_res,
+                      offset, compression)
+
+
+def _write_exr_planes(path, planes, total_res, offset, compression):
+    """A scanline OpenEXR file of planes = [(name, (H, W) float16 or float32 array)], names ascending: HALF
+    or FLOAT channels, ZIP (16 lines a block) or NONE."""
+    assert [n for n, _ in planes] == sorted(n for n, _ in planes)
+    h, w = planes[0][1].shape
     tx, ty = total_res if total_res is not None else (w, h)
     ox, oy = offset
     comp = {"none": 0, "zip": 3}[compression]
     lpb = 16 if comp == 3 else 1
+    ptype = {np.dtype(np.float16): (1, "<f2"), np.dtype(np.float32): (2, "<f4")}
 
     def attr(name, typ, data):
         return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(data)) + data
 
-    chans = b"".join(c.encode() + b"\0" + struct.pack("<iB3xii", 1, 0, 1, 1) for c in "ABGR") + b"\0"
+    chans = b"".join(n.encode() + b"\0" + struct.pack("<iB3xii", ptype[p.dtype][0], 0, 1, 1)
+                     for n, p in planes) + b"\0"
     hdr = struct.pack("<ii", 20000630, 2)
     hdr += attr("channels", "chlist", chans)
     hdr += attr("compression", "compression", bytes([comp]))
@@ -138,14 +184,11 @@ def write_exr(path, rgb, total_res=None, offset=(0, 0), compression="zip"):
     hdr += attr("screenWindowCenter", "v2f", struct.pack("<ff", 0.0, 0.0))
     hdr += attr("screenWindowWidth", "float", struct.pack("<f", 1.0))
     hdr += b"\0"
-    with np.errstate(over="ignore"):
-        half = rgb.astype(np.float16)  # Rgba(float): round to nearest even, overflow to inf
-    alpha = np.ones((h, w), np.float16)
     blocks = []
     for y0 in range(0, h, lpb):
-        raw = b"".join(plane[y].astype("<f2").tobytes()
+        raw = b"".join(plane[y].astype(ptype[plane.dtype][1]).tobytes()
                        for y in range(y0, min(h, y0 + lpb))
-                       for plane in (alpha, half[..., 2], half[..., 1], half[..., 0]))
+                       for _, plane in planes)
         data = raw
         if comp == 3:
             z = zlib.compress(_predict_interleave(raw))

@@ -127,6 +127,21 @@ def _rle_decode(src, expect):
 
 
 def read_exr(path):
+    """ReadImageEXR: the R, G, B channels through HALF slices (missing: 0), (H, W, 3) float32."""
+    planes = read_exr_channels(path)
+    h, w = next(iter(planes.values())).shape
+
+    def half_slice(nm):  # Slice(HALF, ...): every channel type converts to half; missing -> 0.0
+        if nm not in planes:
+            return np.zeros((h, w), np.float32)
+        return planes[nm].astype(np.float32).astype(np.float16).astype(np.float32)
+
+    return np.ascontiguousarray(np.stack([half_slice("R"), half_slice("G"), half_slice("B")], -1))
+
+
+def read_exr_channels(path):
+    """Every channel of a scanline file as stored: {name: (H, W) plane}, in the file's (alphabetical) channel
+    order -- float32 for FLOAT and HALF channels (their values exactly), uint32 for UINT."""
     d = open(path, "rb").read()
     magic, ver = struct.unpack("<ii", d[:8])
     if magic != 20000630:
@@ -165,7 +180,7 @@ def read_exr(path):
     lpb = _LINES[comp]
     nblocks = (h + lpb - 1) // lpb
     offsets = struct.unpack("<%dQ" % nblocks, d[pos:pos + 8 * nblocks])
-    planes = {nm: np.zeros((h, w), np.float32) for nm, _ in chans}
+    planes = {nm: np.zeros((h, w), np.uint32 if pt == 0 else np.float32) for nm, pt in chans}
     for off in offsets:
         yb, size = struct.unpack("<ii", d[off:off + 8])
         raw = d[off + 8:off + 8 + size]
@@ -183,12 +198,6 @@ def read_exr(path):
             for nm, pt in chans:
                 dt, nbt = _PIX[pt]
                 row = np.frombuffer(raw, dt, count=w, offset=p)
-                planes[nm][yb - y0 + li] = row.astype(np.float32)
+                planes[nm][yb - y0 + li] = row
                 p += nbt * w
-
-    def half_slice(nm):  # Slice(HALF, ...): every channel type converts to half; missing -> 0.0
-        if nm not in planes:
-            return np.zeros((h, w), np.float32)
-        return planes[nm].astype(np.float16).astype(np.float32)
-
-    return np.ascontiguousarray(np.stack([half_slice("R"), half_slice("G"), half_slice("B")], -1))
+    return planes

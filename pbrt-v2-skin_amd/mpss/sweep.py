@@ -49,21 +49,33 @@ def _sync():
     torch.cuda.synchronize()
 
 
-def render_frame(ctx, sc, seed=7, tile=256, out=None):
-    """The whole frame in tile x tile rectangles (one mpss_render_tiles call) -> [H, W, 4] XYZW."""
+def render_frame(ctx, sc, seed=7, tile=256, out=None, spectral=False):
+    """The whole frame in tile x tile rectangles (one mpss_render_tiles call) -> [H, W, 4] XYZW. spectral:
+    one mpss_render_tiles_spectral call -> (XYZW, [H, W, 32] band sums, weight sum and 0 per pixel:
+    film.finalize_spectral's input)."""
     import torch
     from mpss import tiles
     rects = tiles.tile_grid(sc.xres, sc.yres, tile)
     bufs = [torch.zeros(((r[3] - r[2]) * (r[1] - r[0]) * 4,), dtype=torch.float32, device="cuda") for r in rects]
-    ctx.render_tiles(sc.spp, seed, rects, [b.data_ptr() for b in bufs])
+    if spectral:
+        sbufs = [torch.zeros(((r[3] - r[2]) * (r[1] - r[0]) * 32,), dtype=torch.float32, device="cuda") for r in rects]
+        ctx.render_tiles_spectral(sc.spp, seed, rects, [b.data_ptr() for b in sbufs], [b.data_ptr() for b in bufs])
+    else:
+        ctx.render_tiles(sc.spp, seed, rects, [b.data_ptr() for b in bufs])
     torch.cuda.synchronize()
     film = np.zeros((sc.yres, sc.xres, 4), np.float32) if out is None else out
     for (x0, x1, y0, y1), b in zip(rects, bufs):
         film[y0:y1, x0:x1] = b.cpu().numpy().reshape(y1 - y0, x1 - x0, 4)
-    return film
+    if not spectral:
+        return film
+    spec = np.zeros((sc.yres, sc.xres, 32), np.float32)
+    for (x0, x1, y0, y1), b in zip(rects, sbufs):
+        spec[y0:y1, x0:x1] = b.cpu().numpy().reshape(y1 - y0, x1 - x0, 32)
+    return film, spec
 
 
-def sweep(sc, rows, mode="update", material=0, seed=1, render_seed=7, tile=256, grid_on_host=None, **cfg_kw):
+def sweep(sc, rows, mode="update", material=0, seed=1, render_seed=7, tile=256, grid_on_host=None, spectral=False,
+          **cfg_kw):
     """Generator over rows of (H, M, E, B): yields (film [H, W, 4] XYZW, seconds, ctx) per row. seconds
     holds setup_s (building a context: scene, BVH upload aside, and its material; 0 for rows that
     build none), material_s (the material's table build), preprocess_s and render_s. mode "update":
@@ -71,7 +83,8 @@ def sweep(sc, rows, mode="update", material=0, seed=1, render_seed=7, tile=256, 
     a new context per row with the row's material (all a library without mpss_update_layeredskin can
     do), material_s then being the part of setup_s spent in mpss_add_layeredskin. ctx is the context
     that rendered the row (valid until the generator is advanced). grid_on_host: the common-grid
-    builder of the material builds (Context.set_grid_builder; None: the library's default)."""
+    builder of the material builds (Context.set_grid_builder; None: the library's default). spectral: every
+    row renders the band cube beside the film, and `film` is render_frame's pair (XYZW, [H, W, 32])."""
     from mpss import pbrtscene
     if mode not in ("update", "fresh"):
         raise ValueError("mode must be 'update' or 'fresh'")
@@ -108,7 +121,7 @@ def sweep(sc, rows, mode="update", material=0, seed=1, render_seed=7, tile=256, 
             _sync()
             secs["preprocess_s"] = time.perf_counter() - t0
             t0 = time.perf_counter()
-            film = render_frame(ctx, sc, render_seed, tile)
+            film = render_frame(ctx, sc, render_seed, tile, spectral=spectral)
             secs["render_s"] = time.perf_counter() - t0
             yield film, secs, ctx
     finally:

@@ -6,6 +6,9 @@ utilities/csv/perms.csv), writing one image per row.
   --mode update   one context; per row the material is rebuilt in place (mpss_update_layeredskin),
                   Preprocess reuses its surface points, the scene buffers stay on the device
   --mode fresh    a new context per row (the only way without mpss_update_layeredskin): the comparison
+  --spectral      every row also renders its 30-band radiance cube (mpss_render_tiles_spectral, one call for
+                  both films) and writes it as perm_NNNN_spectral.exr: apply your own illuminant and sensor
+                  curves to the band radiances instead of the CIE observer baked into the image
 
 Prints one JSON line per permutation (seconds of the material build, Preprocess, render and image
 write) and a summary line (permutations/s over the whole run; median, min and max of each stage).
@@ -68,6 +71,8 @@ def main(argv=None):
                     help="the common-grid builder of the material builds (default: the library's)")
     ap.add_argument("--split", action="store_true", help="split the material build (extra work per row)")
     ap.add_argument("--no-write", action="store_true", help="skip the image files (timing runs)")
+    ap.add_argument("--spectral", action="store_true", help="also render the 30-band radiance cube of every row "
+                    "and write it beside the image as perm_NNNN_spectral.exr (30 FLOAT channels S0.<centre>nm)")
     args = ap.parse_args(argv)
 
     import mpss
@@ -85,10 +90,16 @@ def main(argv=None):
     t_row = t_run
     for i, (xyzw, secs, ctx) in enumerate(sw.sweep(sc, rows, mode=args.mode, material=args.material,
                                                     grid_on_host=None if args.grid_builder is None else
-                                                    args.grid_builder == "host")):
+                                                    args.grid_builder == "host", spectral=args.spectral)):
         t0 = time.perf_counter()
+        spec = None
+        if args.spectral:
+            xyzw, spec = xyzw
         if not args.no_write:
             film.write_image(os.path.join(args.out, "perm_%04d.%s" % (i, args.format)), film.finalize(xyzw))
+            if spec is not None:
+                film.write_spectral_exr(os.path.join(args.out, "perm_%04d_spectral.exr" % i),
+                                        film.finalize_spectral(spec))
         secs["write_s"] = time.perf_counter() - t0
         secs["total_s"] = time.perf_counter() - t_row
         if args.split:
